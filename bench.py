@@ -2,6 +2,12 @@
 """bench.py -- Gaussians rasterized/sec (fwd+bwd) on MI355X, BASELINE.json's metric.
 
   python bench.py --gpus N --steps K --warmup W [--config c3|c2|c5shape|ref16k|c4|c5] [--mode graph|eager|eager-st]
+                  [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps of --mode and prints the result line (`value`, `ms_per_step`, ...).  --full
+also measures everything else below (the other modes, the event-timed median, `long_run`, the collectives' exposed cost, the
+per-kernel timings and rooflines, the CPU baselines and the reference's kernels).  --dump-outputs DIR writes what the last
+timed step computed (images, radii, gradients) as DIR/<name>.npy, float32, from inputs that are the same run to run.
 
 N > 1 without a launcher: the script re-executes itself under `python -m torch.distributed.run --nproc-per-node N`
 (one rank per GPU, RCCL); under a launcher (RANK / WORLD_SIZE set) it checks WORLD_SIZE == N.
@@ -12,7 +18,7 @@ F=32, one look-at view per GPU per step, production negative-focal cameras, inpu
 + one backward of the rasterizer through the public GaussianRasterizer autograd API (+ one all-reduce of the per-Gaussian
 parameter gradients when N>1; weak scaling: every GPU renders its own view of the replicated Gaussian set).
 
-Modes (all are timed and reported under "modes_ms_per_step"; `value` comes from --mode, default graph):
+Modes (with --full all are timed and reported under "modes_ms_per_step"; `value` comes from --mode, default graph):
   graph     the step captured once with torch.cuda.graph through the PUBLIC autograd API and replayed (possible because
             nothing in the library synchronises; needs --forward-mode async, the opt-in).  The headline: a replay needs ~10 us
             of host time per step, so a 20-step region of 3 ms does not feel a host hiccup; one replay costs ~5 us more than
@@ -29,8 +35,8 @@ Modes (all are timed and reported under "modes_ms_per_step"; `value` comes from 
   eager     the same with torch's default autograd threading: every backward is handed to the engine's device thread and
             back (two thread wake-ups per step): host-bound at this step size, printed beside the headline.
 
-EXACTLY --steps steps are timed for `value` / `ms_per_step` / `steps`.  A K-step region shorter than 50 ms is additionally
-re-measured over a longer region and reported as `long_run` (the short region carries ~0.1 ms of bracket overhead).
+EXACTLY --steps steps are timed for `value` / `ms_per_step` / `steps`.  With --full a K-step region shorter than 50 ms is
+additionally re-measured over a longer region and reported as `long_run` (the short region carries ~0.1 ms of bracket overhead).
 
 Dynamic configs (BASELINE configs[3] / [4], strong scaling: the work of a step is fixed, the ranks share it --
 manigaussian_amd.parallel.DynamicPlan):
@@ -44,7 +50,7 @@ manigaussian_amd.parallel.DynamicPlan):
   l2(feature) -> backward: reduce-scatter, MLP backward into the flat parameter-gradient bucket (the one all-reduce,
   asynchronous) and into this rank's rows of point_latent (a local leaf, complete without a collective).
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline      the dominant kernel (render backward) timed live with HIP events on its launch stream, against the HBM
                 roof: `achieved` = the bytes THIS dataflow has to move per launch (every array once) / duration,
                 `traffic` = counter bytes per launch from the committed passes of the same binary, `frac` <= 1 by
@@ -131,7 +137,17 @@ def parse():
                                                                         "beside the cpu_baseline")
     ap.add_argument("--calibrate", action="store_true", help="counter passes: launch the library's known-instruction-mix "
                                                              "kernel a few times first (scripts/sq_counters.py checks it)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline also measure the other modes, the event-timed median, the longer re-measure, the "
+                         "collectives' exposed cost, per-kernel timings and rooflines, the MLP roof, the CPU baselines and the "
+                         "reference's kernels (a plain run does set-up, warm-up and the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path computed in its last step (images, radii, "
+                         "gradients) as DIR/<name>.npy, float32, at most 64 MB in all (a fixed, seeded sample above that)")
+    args = ap.parse_args()
+    if args.strict_roofline and not args.full:
+        ap.error("--strict-roofline checks the rooflines, which only --full measures")
+    return args
 
 
 def self_launch(args):
@@ -227,6 +243,31 @@ def cpu_baseline_dynamic(syn, sc, cam, d_color, d_feat, P, timesteps, renders_to
             "sample": f"MLP (torch CPU, {torch.get_num_threads()} threads): {len(times)} fwd+bwd passes over {n} of {P} points, "
                       f"best {min(times) * 1e3:.0f} ms, scaled by P/{n} -> {t_mlp * 1e3:.0f} ms per timestep; rasterizer: "
                       f"{rast['sample']}; step = {timesteps} x MLP + {renders_total} x render = {t_step * 1e3:.0f} ms"}
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32 (float64 kept).  Above DUMP_LIMIT_BYTES in all, the large
+    arrays are cut to a fixed, seeded sample of their flattened elements (same indices for the same shape, run to run)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    host = {n: t.detach().to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+            for n, t in arrays.items()}
+    budget = DUMP_LIMIT_BYTES - 4096 * len(host)  # (.npy headers)
+    small = 1 << 18  # arrays of at most this many elements are always whole
+    if sum(a.nbytes for a in host.values()) > budget:
+        big = {n for n, a in host.items() if a.size > small}
+        room = budget - sum(host[n].nbytes for n in host if n not in big)
+        frac = room / sum(host[n].nbytes for n in big)
+        for n in sorted(big):
+            a = host[n].reshape(-1)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, int(a.size * frac), replace=False))
+            host[n] = a[idx]
+    for n, a in host.items():
+        np.save(os.path.join(path, n + ".npy"), np.ascontiguousarray(a))
 
 
 def lib_hash():
@@ -369,6 +410,7 @@ def main():
     P, F, W, H, V, NR = cfg["P"], cfg["F"], cfg["size"], cfg["size"], max(1, cfg["views"]), cfg["renders"]
     deform = bool(cfg.get("deform"))
     M = 4
+    torch.manual_seed(0)  # the same inputs run to run (the deformation field's initial weights come from torch's generator)
     sc = syn.make_scene(P, F=F, M=M, seed=0)  # identical on every rank: the replicated Gaussian set
     params = {k: v.to(dev).requires_grad_(True) for k, v in sc.items()}
     plan = None
@@ -434,6 +476,7 @@ def main():
             args.mode = "eager-st"  # collectives inside the step (all-gather / reduce-scatter): the step is enqueued eagerly
 
     last_radii = [None]
+    last_out = {}  # --dump-outputs only: what the step hands its caller (detached: no autograd node is kept alive)
 
     def render_once(i):
         if V > 1:
@@ -465,6 +508,11 @@ def main():
                 last_radii[0] = radii
                 loss = ((color - gr["tgt_c"]) ** 2).sum() / n_c + 0.01 * ((feat - gr["tgt_f"]) ** 2).sum() / n_f
                 loss.backward()
+                if args.dump_outputs:
+                    last_out.update({f"color_t{gr['t']}": color.detach(), f"feat_t{gr['t']}": feat.detach(),
+                                     f"radii_t{gr['t']}": radii.detach()})
+            if args.dump_outputs:
+                last_out.update(grad_mlp_flat=bucket.flat, grad_point_latent=point_latent.grad)
             return [bucket.flat]
         out = None
         for i in range(NR):
@@ -473,6 +521,10 @@ def main():
             dc, df = (d_color, d_feat) if V > 1 else cots[i]
             gs = torch.autograd.grad([color, feat], plist, [dc, df])
             out = gs if out is None else out  # NR > 1: the renders are independent; the last ones' gradients stand in
+            if args.dump_outputs:
+                sfx = f"_{i}" if NR > 1 else ""
+                last_out.update({"color" + sfx: color.detach(), "feat" + sfx: feat.detach(), "radii" + sfx: radii.detach()})
+                last_out.update({f"grad_{n}{sfx}": g for n, g in zip(params, gs)})
         return out
 
     # ---- one "stepper" per mode: step() enqueues a whole step, grads() are the tensors an all-reduce takes ----
@@ -487,6 +539,9 @@ def main():
             self.last = compute_step()
             return self.last
 
+        def outputs(self):
+            return dict(last_out)
+
     class Graphed:
         """The step captured into HIP graphs.  Two graphs with their own output buffers alternate when N > 1 so that one
         step's all-reduce may overlap the next step's replay."""
@@ -500,13 +555,14 @@ def main():
             with torch.cuda.stream(side):
                 compute_step()
             torch.cuda.current_stream().wait_stream(side)
-            self.graphs, self.outs, self.i = [], [], 0
+            self.graphs, self.outs, self.dumps, self.i = [], [], [], 0
             for _ in range(nbuf):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
                     o = compute_step()
                 self.graphs.append(g)
                 self.outs.append(o)
+                self.dumps.append(dict(last_out))  # (the captured step's own buffers: a replay rewrites them)
 
         def next_slot(self):
             return self.i % len(self.graphs)
@@ -517,6 +573,9 @@ def main():
             self.graphs[k].replay()
             self.last = self.outs[k]
             return self.last
+
+        def outputs(self):
+            return self.dumps[(self.i - 1) % len(self.graphs)]
 
     pending = {}  # gradient buffer -> work handle of its all-reduce still in flight
 
@@ -577,6 +636,7 @@ def main():
         return el
 
     extra_warmup = {}
+    dumped = []
 
     from manigaussian_amd import _C as _shim
 
@@ -603,8 +663,12 @@ def main():
         run(stepper, extra - 2, collective)
         extra_warmup[mode] = extra
         el = timed(stepper, steps, collective)  # EXACTLY the K steps that were asked for
+        if args.dump_outputs and mode == args.mode and not dumped:
+            dumped.append(mode)
+            if rank == 0:
+                dump_outputs(args.dump_outputs, stepper.outputs())
         long_run = None
-        if el * 1e3 < MIN_TIMED_MS:  # a short region carries the brackets' overhead: measure a longer one BESIDE it
+        if args.full and el * 1e3 < MIN_TIMED_MS:  # a short region carries the brackets' overhead: measure a longer one BESIDE it
             k2 = int(steps * MIN_TIMED_MS / (el * 1e3) * 1.2) + 1
             long_run = (timed(stepper, k2, collective), k2)
         check_status(dev)
@@ -619,7 +683,7 @@ def main():
     all_modes = ("graph", "eager", "eager-st", "eager-safe", "eager-ctypes")
     if deform and (plan.group_size > 1 or plan.group is not None):
         all_modes = ("eager", "eager-st", "eager-safe")
-    modes = [args.mode] if args.only_mode else [args.mode] + [m for m in all_modes if m != args.mode]
+    modes = [args.mode] if (args.only_mode or not args.full) else [args.mode] + [m for m in all_modes if m != args.mode]
     results, errors, long_runs = {}, {}, {}
     headline_stepper = None
     for m in modes:
@@ -641,7 +705,7 @@ def main():
 
     # SURVEY.md 8d's protocol beside the bracketed mean: a hipEvent pair per step on the work stream, median over <= 100 steps
     median_ms = None
-    if headline_stepper is not None:
+    if args.full and headline_stepper is not None:
         torch.autograd.set_multithreading_enabled(mode != "eager-st")
         n_med = min(max(steps, 20), 100)
         old_fm = manigaussian_amd.set_forward_mode("safe") if mode == "eager-safe" else None
@@ -666,81 +730,83 @@ def main():
     if coll_on:
         fa = flat_alias(headline_stepper.last) if headline_stepper is not None else None
         ar_bytes = int(fa.numel() * 4) if fa is not None else int(sum(g.numel() for g in headline_stepper.last) * 4)
-    if coll_on:  # what the collective costs on top of the compute: the same K steps without it
+    if coll_on and args.full:  # what the collective costs on top of the compute: the same K steps without it
         el0, k0, _, lr0 = measure(mode, steps, 5, collective=False)
         lr1 = long_runs.get(mode)
         with_ms = (lr1[0] / lr1[1]) if lr1 else elapsed / steps
         without_ms = (lr0[0] / lr0[1]) if lr0 else el0 / k0
         exposed_ms = max(0.0, with_ms - without_ms) * 1e3
 
-    # every kernel timed live: hipEvents around each launch on its launch stream (eager steps: events cannot be read back
-    # from inside a captured graph), an untimed extra pass
-    torch.autograd.set_multithreading_enabled(False)
-    _lib.profile_read(reset=True)
-    _lib.set_option("profile", 2)
-    e = Eager()
-    n_prof = min(max(args.steps, 20), 100) if not deform else min(max(args.steps, 4), 10)
-    run(e, n_prof, collective=False)
-    sync_all()
-    _lib.set_option("profile", 0)
-    prof = _lib.profile_read(reset=True)
-    torch.autograd.set_multithreading_enabled(True)
-    stages = {k: (ms / max(c, 1)) for k, (ms, c) in prof.items()}
-
-    # what ONE launch of the render kernels covers on this rank: instances (R), visible Gaussians, (block, Gaussian)
-    # incidences and chunks of the forward -> backward state (mgs_forward_stats, a blocking diagnostic)
-    import ctypes
     launches_per_step = len(groups) if deform else NR
     launch_views = len(groups[0]["views"]) if deform else V
-    torch.cuda.synchronize()
-    # (a forward of its own whose outputs stay alive: the autograd node keeps the workspaces the statistics are read from)
-    with _shim.use_compiled(False):  # (the ctypes shim: its autograd node exposes the forward's handle)
-        color_s, feat_s, radii_s = deform_group(groups[0]) if deform else render_once(0)
-    torch.cuda.synchronize()
-    handle = color_s.grad_fn.num_rendered  # the forward's ForwardHandle (manigaussian_amd/_C.py)
-    R = handle.binned()    # (Gaussian, tile) instances the kernels actually move
-    R_reference = int(handle)  # the reference's num_rendered (3-sigma rects), what the call hands back
-    nvis = int((radii_s > 0).sum().item())
-    inc_, ch_, pc_ = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
-    _lib.check(_lib.lib().mgs_forward_stats(ctypes.byref(handle.a), launch_views if (deform or V > 1) else 0,
-                                            ctypes.byref(inc_), ctypes.byref(ch_), ctypes.byref(pc_), None), "mgs_forward_stats")
-    incidences, chunks, pixel_chunks = int(inc_.value), int(ch_.value), int(pc_.value)
-    del color_s, feat_s, radii_s, handle
+    prof, stages, mlp_block = {}, {}, None
+    if args.full:
+        # every kernel timed live: hipEvents around each launch on its launch stream (eager steps: events cannot be read back
+        # from inside a captured graph), an untimed extra pass
+        torch.autograd.set_multithreading_enabled(False)
+        _lib.profile_read(reset=True)
+        _lib.set_option("profile", 2)
+        e = Eager()
+        n_prof = min(max(args.steps, 20), 100) if not deform else min(max(args.steps, 4), 10)
+        run(e, n_prof, collective=False)
+        sync_all()
+        _lib.set_option("profile", 0)
+        prof = _lib.profile_read(reset=True)
+        torch.autograd.set_multithreading_enabled(True)
+        stages = {k: (ms / max(c, 1)) for k, (ms, c) in prof.items()}
 
-    # the deformation MLP apart from the rasterizer: forward + backward of this rank's points, hipEvent-timed
-    mlp_block = None
-    if deform:
-        from manigaussian_amd.deform import assemble_deform_input
-        n_loc = int(point_latent.shape[0])
-        gr = groups[0]
-        lo, hi = plan.point_rows(P)
-
-        def mlp_only():
-            zx = assemble_deform_input(point_latent, z_feature, params["means3D"].detach()[lo:hi], params["shs"].detach()[lo:hi],
-                                       params["rotations"].detach()[lo:hi], params["scales"].detach()[lo:hi],
-                                       params["opacities"].detach()[lo:hi], None, gr["action"])
-            delta, _ = field.mlp(zx)
-            delta.backward(torch.ones_like(delta))
-        for _ in range(2):
-            mlp_only()
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        n_it = 5
-        ev0.record()
-        for _ in range(n_it):
-            mlp_only()
-        ev1.record()
+        # what ONE launch of the render kernels covers on this rank: instances (R), visible Gaussians, (block, Gaussian)
+        # incidences and chunks of the forward -> backward state (mgs_forward_stats, a blocking diagnostic)
+        import ctypes
         torch.cuda.synchronize()
-        mlp_ms = ev0.elapsed_time(ev1) / n_it
-        point_latent.grad = None
-        macs = 70 * 512 + 3 * 128 * 512 + 10 * 512 * 512 + 512 * 7  # per point: lin_in, 3 lin_z, 5 blocks x 2, lin_out
-        flops = 3 * 2 * macs * n_loc                                  # forward + data gradients + weight gradients
-        mlp_block = {"bound": "mfma", "dtype": "f32", "achieved": flops / (mlp_ms * 1e-3) / 1e12,
-                     "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": flops / (mlp_ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS, "flops_per_timestep_per_rank": flops,
-                     "ms_per_timestep_per_rank": mlp_ms, "points_per_rank": n_loc,
-                     "what": "input assembly + ResnetFC forward + backward (fp32 GEMMs on hipBLASLt / rocBLAS through torch, "
-                             "fused HIP elementwise passes) of this rank's points for one timestep, hipEvent-timed apart from "
-                             "the rasterizer; FLOPs = 3 x 2 x 3.28 M MACs per point (the elementwise passes add time, no FLOPs)"}
+        # (a forward of its own whose outputs stay alive: the autograd node keeps the workspaces the statistics are read from)
+        with _shim.use_compiled(False):  # (the ctypes shim: its autograd node exposes the forward's handle)
+            color_s, feat_s, radii_s = deform_group(groups[0]) if deform else render_once(0)
+        torch.cuda.synchronize()
+        handle = color_s.grad_fn.num_rendered  # the forward's ForwardHandle (manigaussian_amd/_C.py)
+        R = handle.binned()    # (Gaussian, tile) instances the kernels actually move
+        R_reference = int(handle)  # the reference's num_rendered (3-sigma rects), what the call hands back
+        nvis = int((radii_s > 0).sum().item())
+        inc_, ch_, pc_ = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(_lib.lib().mgs_forward_stats(ctypes.byref(handle.a), launch_views if (deform or V > 1) else 0,
+                                                ctypes.byref(inc_), ctypes.byref(ch_), ctypes.byref(pc_), None), "mgs_forward_stats")
+        incidences, chunks, pixel_chunks = int(inc_.value), int(ch_.value), int(pc_.value)
+        del color_s, feat_s, radii_s, handle
+
+        # the deformation MLP apart from the rasterizer: forward + backward of this rank's points, hipEvent-timed
+        mlp_block = None
+        if deform:
+            from manigaussian_amd.deform import assemble_deform_input
+            n_loc = int(point_latent.shape[0])
+            gr = groups[0]
+            lo, hi = plan.point_rows(P)
+
+            def mlp_only():
+                zx = assemble_deform_input(point_latent, z_feature, params["means3D"].detach()[lo:hi], params["shs"].detach()[lo:hi],
+                                           params["rotations"].detach()[lo:hi], params["scales"].detach()[lo:hi],
+                                           params["opacities"].detach()[lo:hi], None, gr["action"])
+                delta, _ = field.mlp(zx)
+                delta.backward(torch.ones_like(delta))
+            for _ in range(2):
+                mlp_only()
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            n_it = 5
+            ev0.record()
+            for _ in range(n_it):
+                mlp_only()
+            ev1.record()
+            torch.cuda.synchronize()
+            mlp_ms = ev0.elapsed_time(ev1) / n_it
+            point_latent.grad = None
+            macs = 70 * 512 + 3 * 128 * 512 + 10 * 512 * 512 + 512 * 7  # per point: lin_in, 3 lin_z, 5 blocks x 2, lin_out
+            flops = 3 * 2 * macs * n_loc                                  # forward + data gradients + weight gradients
+            mlp_block = {"bound": "mfma", "dtype": "f32", "achieved": flops / (mlp_ms * 1e-3) / 1e12,
+                         "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                         "frac": flops / (mlp_ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS, "flops_per_timestep_per_rank": flops,
+                         "ms_per_timestep_per_rank": mlp_ms, "points_per_rank": n_loc,
+                         "what": "input assembly + ResnetFC forward + backward (fp32 GEMMs on hipBLASLt / rocBLAS through torch, "
+                                 "fused HIP elementwise passes) of this rank's points for one timestep, hipEvent-timed apart from "
+                                 "the rasterizer; FLOPs = 3 x 2 x 3.28 M MACs per point (the elementwise passes add time, no FLOPs)"}
 
     dev_ids = [None] * world
     if world > 1:
@@ -752,85 +818,86 @@ def main():
         ms_step = elapsed / steps * 1e3
         renders = launches_per_step * launch_views   # renders per GPU per step
         value = P * renders_total * steps / elapsed  # whole job: every render of every rank
-        npix = W * H * launch_views  # pixels one launch covers
-        T_tiles = ((W + 15) // 16) * ((H + 15) // 16) * launch_views
-        pre_block = 512 if P <= 131072 else 1024  # (csrc/mgs_common.h pre_block())
-        nblk = launch_views * ((P + pre_block - 1) // pre_block)
-        bucket = _lib.get_option("bin_mode") == 2 and T_tiles <= 4096
-        direct = bucket and prof.get("bin_scatter", (0.0, 0))[1] == 0  # no scatter launch was timed: the preprocess wrote the keys
-        KERNELS = [k for k in KERNELS_BUCKET if not (direct and k[0] == "bin_scatter")] if bucket else KERNELS_SEGSORT
-        mb = model_bytes(P, launch_views, M, F, npix, T_tiles, R, nvis, incidences, pixel_chunks, nblk, bucket, direct)
-        so_hash = lib_hash()
-        cfiles = counter_files(args.config, launch_views if not deform else 1) if not deform else \
-            [f"r06_sq_counters_{args.config}.json", f"r05_sq_counters_{args.config}.json", f"r04_sq_counters_{args.config}.json"]
         violations = []
+        if args.full:
+            npix = W * H * launch_views  # pixels one launch covers
+            T_tiles = ((W + 15) // 16) * ((H + 15) // 16) * launch_views
+            pre_block = 512 if P <= 131072 else 1024  # (csrc/mgs_common.h pre_block())
+            nblk = launch_views * ((P + pre_block - 1) // pre_block)
+            bucket = _lib.get_option("bin_mode") == 2 and T_tiles <= 4096
+            direct = bucket and prof.get("bin_scatter", (0.0, 0))[1] == 0  # no scatter launch was timed: the preprocess wrote the keys
+            KERNELS = [k for k in KERNELS_BUCKET if not (direct and k[0] == "bin_scatter")] if bucket else KERNELS_SEGSORT
+            mb = model_bytes(P, launch_views, M, F, npix, T_tiles, R, nvis, incidences, pixel_chunks, nblk, bucket, direct)
+            so_hash = lib_hash()
+            cfiles = counter_files(args.config, launch_views if not deform else 1) if not deform else \
+                [f"r06_sq_counters_{args.config}.json", f"r05_sq_counters_{args.config}.json", f"r04_sq_counters_{args.config}.json"]
 
-        def hbm_line(stage, substr, label):
-            """The HBM line of one kernel: model bytes per launch / its average launch duration (hipEvents on the launch
-            stream) against 8 TB/s; `traffic` = HBM bytes per launch by the counters (2 * FETCH_SIZE + WRITE_SIZE KiB, the
-            guide's gfx950 correction) from the committed passes of THIS binary, and the fraction they give."""
-            avg_ms, (tot_ms, launches) = stages.get(stage, 0.0), prof.get(stage, (0.0, 0))
-            cnt, why = committed_counters(substr, so_hash, cfiles)
-            traffic = cnt.get("hbm_bytes_per_launch") if cnt else None
-            ach = mb[stage] / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-            rb = {"kernel": label, "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                  "frac": ach / HBM_PEAK_GBS, "traffic": traffic, "avg_launch_ms": avg_ms, "launches": launches,
-                  "algorithmic_bytes_per_launch": mb[stage],
-                  "frac_by_counter_bytes": (traffic / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic and avg_ms > 0 else None,
-                  "traffic_over_algorithmic": (traffic / mb[stage]) if traffic and mb[stage] else None,
-                  "counters_note": why}
-            for k in ("frac", "frac_by_counter_bytes"):
-                if rb[k] is not None and rb[k] > 1.0:
-                    violations.append(f"{label}: {k} = {rb[k]:.3f}")
-            return rb, cnt
+            def hbm_line(stage, substr, label):
+                """The HBM line of one kernel: model bytes per launch / its average launch duration (hipEvents on the launch
+                stream) against 8 TB/s; `traffic` = HBM bytes per launch by the counters (2 * FETCH_SIZE + WRITE_SIZE KiB, the
+                guide's gfx950 correction) from the committed passes of THIS binary, and the fraction they give."""
+                avg_ms, (tot_ms, launches) = stages.get(stage, 0.0), prof.get(stage, (0.0, 0))
+                cnt, why = committed_counters(substr, so_hash, cfiles)
+                traffic = cnt.get("hbm_bytes_per_launch") if cnt else None
+                ach = mb[stage] / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+                rb = {"kernel": label, "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                      "frac": ach / HBM_PEAK_GBS, "traffic": traffic, "avg_launch_ms": avg_ms, "launches": launches,
+                      "algorithmic_bytes_per_launch": mb[stage],
+                      "frac_by_counter_bytes": (traffic / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic and avg_ms > 0 else None,
+                      "traffic_over_algorithmic": (traffic / mb[stage]) if traffic and mb[stage] else None,
+                      "counters_note": why}
+                for k in ("frac", "frac_by_counter_bytes"):
+                    if rb[k] is not None and rb[k] > 1.0:
+                        violations.append(f"{label}: {k} = {rb[k]:.3f}")
+                return rb, cnt
 
-        by_kernel = {}
-        cnts = {}
-        for stage, substr, label in KERNELS:
-            by_kernel[stage], cnts[stage] = hbm_line(stage, substr, label)
+            by_kernel = {}
+            cnts = {}
+            for stage, substr, label in KERNELS:
+                by_kernel[stage], cnts[stage] = hbm_line(stage, substr, label)
 
-        def limiter(stage):
-            """What the counters say limits a render kernel: no throughput roof is near -- the waves spend their cycles
-            waiting on dependent instructions and on memory / LDS / barriers (SQ_WAIT_*)."""
-            cnt, avg_ms = cnts[stage], stages.get(stage, 0.0)
-            if not (cnt and cnt.get("SQ_INSTS_VALU") and avg_ms > 0):
-                return None
-            cycles = avg_ms * 1e-3 * 2.4e9  # upper bound: 2.4 GHz peak clock
-            gips = cnt["SQ_INSTS_VALU"] / (avg_ms * 1e-3) / 1e9
-            wc = cnt.get("SQ_WAVE_CYCLES") or 0.0
-            return {"summary": "latency (dependent issue + waits): HBM, VALU issue and the matrix pipe are all far from peak",
-                    "valu_issue": {"achieved": gips, "peak": VALU_PEAK_GIPS, "unit": "G wave-instr/s", "frac": gips / VALU_PEAK_GIPS},
-                    "valu_busy_frac_of_simd_cycles": (cnt.get("SQ_ACTIVE_INST_VALU", 0.0) * 4.0) / (1024 * cycles),
-                    "mfma_busy_frac_of_simd_cycles": cnt.get("SQ_VALU_MFMA_BUSY_CYCLES", 0.0) / (1024 * cycles),
-                    "wave_cycles_split": {k: (cnt[k] / wc if wc and k in cnt else None)
-                                          for k in ("SQ_ACTIVE_INST_ANY", "SQ_WAIT_INST_ANY", "SQ_WAIT_ANY")},
-                    "per_launch": {k: cnt.get(k) for k in ("SQ_WAVES", "SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_MFMA",
-                                                           "SQ_INSTS_LDS", "SQ_LDS_BANK_CONFLICT", "SQ_INSTS_VMEM_RD",
-                                                           "SQ_INSTS_VMEM_WR")}}
+            def limiter(stage):
+                """What the counters say limits a render kernel: no throughput roof is near -- the waves spend their cycles
+                waiting on dependent instructions and on memory / LDS / barriers (SQ_WAIT_*)."""
+                cnt, avg_ms = cnts[stage], stages.get(stage, 0.0)
+                if not (cnt and cnt.get("SQ_INSTS_VALU") and avg_ms > 0):
+                    return None
+                cycles = avg_ms * 1e-3 * 2.4e9  # upper bound: 2.4 GHz peak clock
+                gips = cnt["SQ_INSTS_VALU"] / (avg_ms * 1e-3) / 1e9
+                wc = cnt.get("SQ_WAVE_CYCLES") or 0.0
+                return {"summary": "latency (dependent issue + waits): HBM, VALU issue and the matrix pipe are all far from peak",
+                        "valu_issue": {"achieved": gips, "peak": VALU_PEAK_GIPS, "unit": "G wave-instr/s", "frac": gips / VALU_PEAK_GIPS},
+                        "valu_busy_frac_of_simd_cycles": (cnt.get("SQ_ACTIVE_INST_VALU", 0.0) * 4.0) / (1024 * cycles),
+                        "mfma_busy_frac_of_simd_cycles": cnt.get("SQ_VALU_MFMA_BUSY_CYCLES", 0.0) / (1024 * cycles),
+                        "wave_cycles_split": {k: (cnt[k] / wc if wc and k in cnt else None)
+                                              for k in ("SQ_ACTIVE_INST_ANY", "SQ_WAIT_INST_ANY", "SQ_WAIT_ANY")},
+                        "per_launch": {k: cnt.get(k) for k in ("SQ_WAVES", "SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_MFMA",
+                                                               "SQ_INSTS_LDS", "SQ_LDS_BANK_CONFLICT", "SQ_INSTS_VMEM_RD",
+                                                               "SQ_INSTS_VMEM_WR")}}
 
-        roof = dict(by_kernel["render_bwd"], kernel="K8 render backward (gm_bwd_kernel)", lib_build_id=so_hash)
-        roof["limiter"] = limiter("render_bwd")
-        bwd_ms = stages.get("render_bwd", 0.0)
-        s8d = R * (112 + 12 * F) + npix * (20 + 4 * F)
-        roof["survey_8d_charge"] = {
-            "bytes_per_launch": s8d, "frac_if_charged": (s8d / (bwd_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if bwd_ms > 0 else None,
-            "note": "SURVEY.md 8d's K8 rows R(112+12F) + N(20+4F) charge the reference's per-INSTANCE read-modify-write "
-                    "atomics, which this kernel never issues (register / LDS reduction, one atomic row per (block, Gaussian)): "
-                    "not a bound of this dataflow -- it exceeds 1 at large R / P -- and kept only so that earlier rounds' "
-                    "numbers stay comparable"}
-        roof_fwd = dict(by_kernel["render_fwd"], kernel="K7 render forward (coop_fwd_pairs_kernel)")
-        roof_fwd["limiter"] = limiter("render_fwd")
-        path_model = sum(mb[k] for k, _, _ in KERNELS) * launches_per_step
-        path_traffic = None
-        if all(by_kernel[k]["traffic"] for k in by_kernel):
-            path_traffic = sum(by_kernel[k]["traffic"] for k in by_kernel) * launches_per_step
-        s8d_path = (launch_views * P * (434 + 48 * M + 4 * F) + R * (196 + 16 * F) + npix * (40 + 8 * F)) * launches_per_step
-        rast_ms = sum(stages.get(k, 0.0) for k, _, _ in KERNELS) * launches_per_step  # the rasterizer's kernels per step
-        path_frac = path_model / (rast_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if rast_ms > 0 else None
-        if path_frac is not None and path_frac > 1.0:
-            violations.append(f"path_hbm: frac = {path_frac:.3f}")
-        if mlp_block is not None and mlp_block["frac"] > 1.0:
-            violations.append(f"roofline_mlp: frac = {mlp_block['frac']:.3f}")
+            roof = dict(by_kernel["render_bwd"], kernel="K8 render backward (gm_bwd_kernel)", lib_build_id=so_hash)
+            roof["limiter"] = limiter("render_bwd")
+            bwd_ms = stages.get("render_bwd", 0.0)
+            s8d = R * (112 + 12 * F) + npix * (20 + 4 * F)
+            roof["survey_8d_charge"] = {
+                "bytes_per_launch": s8d, "frac_if_charged": (s8d / (bwd_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if bwd_ms > 0 else None,
+                "note": "SURVEY.md 8d's K8 rows R(112+12F) + N(20+4F) charge the reference's per-INSTANCE read-modify-write "
+                        "atomics, which this kernel never issues (register / LDS reduction, one atomic row per (block, Gaussian)): "
+                        "not a bound of this dataflow -- it exceeds 1 at large R / P -- and kept only so that earlier rounds' "
+                        "numbers stay comparable"}
+            roof_fwd = dict(by_kernel["render_fwd"], kernel="K7 render forward (coop_fwd_pairs_kernel)")
+            roof_fwd["limiter"] = limiter("render_fwd")
+            path_model = sum(mb[k] for k, _, _ in KERNELS) * launches_per_step
+            path_traffic = None
+            if all(by_kernel[k]["traffic"] for k in by_kernel):
+                path_traffic = sum(by_kernel[k]["traffic"] for k in by_kernel) * launches_per_step
+            s8d_path = (launch_views * P * (434 + 48 * M + 4 * F) + R * (196 + 16 * F) + npix * (40 + 8 * F)) * launches_per_step
+            rast_ms = sum(stages.get(k, 0.0) for k, _, _ in KERNELS) * launches_per_step  # the rasterizer's kernels per step
+            path_frac = path_model / (rast_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if rast_ms > 0 else None
+            if path_frac is not None and path_frac > 1.0:
+                violations.append(f"path_hbm: frac = {path_frac:.3f}")
+            if mlp_block is not None and mlp_block["frac"] > 1.0:
+                violations.append(f"roofline_mlp: frac = {mlp_block['frac']:.3f}")
         out = {
             "metric": "Gaussians rasterized/sec (fwd+bwd), 128x128, 32 feat-ch; HBM GB/s vs peak",
             "value": value, "unit": "Gaussians/s", "n_gpus": n_gpus, "steps": steps, "warmup": args.warmup,
@@ -848,12 +915,9 @@ def main():
                        "name": args.config, "P": P, "W": W, "H": H, "F": F, "M": M,
                        "views_per_gpu": (renders if deform else V), "timesteps_per_step": cfg.get("timesteps", 1) if deform else 1,
                        "renders_per_step_per_gpu": renders, "renders_per_step_total": renders_total,
-                       "render_launch_views": launch_views, "num_rendered_R": int(R), "R_over_P": R / (P * launch_views),
-                       "num_rendered_reference": int(R_reference),
-                       "visible_gaussians_per_launch": nvis, "block_gaussian_incidences_per_launch": incidences,
-                       "chunks_per_launch": chunks, "pixel_chunks_per_launch": pixel_chunks,
+                       "render_launch_views": launch_views,
                        "tight_bins": _lib.get_option("tight_bins"), "fast_exp": _lib.get_option("fast_exp"),
-                       "bin_mode": _lib.get_option("bin_mode"), "direct_binning": bool(direct),
+                       "bin_mode": _lib.get_option("bin_mode"),
                        "deformation": ("DeformationField per timestep: HIP input assembly -> fp32 MLP 70->512x5->7 (torch GEMMs, "
                                        "fused HIP elementwise passes) -> HIP apply; gradients of the MLP parameters (one flat "
                                        "bucket) and of point_latent") if deform else None,
@@ -888,41 +952,50 @@ def main():
                                      "of one rank); exposed time = API + kernel-launch cost of the collectives, no transport. "
                                      "predicted_ring_allreduce_ms = 2 (N-1)/N x bytes at 153 GB/s per xGMI link direction: a "
                                      "prediction, never measured by the builder (one GPU)") if dry else None},
-            "roofline": roof, "roofline_fwd": roof_fwd, "roofline_by_kernel": by_kernel,
-            "roofline_mlp": mlp_block,
-            "path_hbm": {"algorithmic_bytes_per_step_per_gpu": path_model,
-                         "kernel_ms_per_step_per_gpu": rast_ms,
-                         "achieved_GBps": (path_model / (rast_ms * 1e-3) / 1e9) if rast_ms > 0 else None,
-                         "frac_of_peak": path_frac,
-                         "counter_bytes_per_step_per_gpu": path_traffic,
-                         "frac_of_peak_by_counter_bytes": (path_traffic / (rast_ms * 1e-3) / 1e9 / HBM_PEAK_GBS)
-                         if path_traffic and rast_ms > 0 else None,
-                         "survey_8d_bytes_per_step_per_gpu": s8d_path,
-                         "note": "the rasterizer's kernels (five with the direct bucket-rank binning, six with a scatter launch, seven with segment sort + merge): model bytes (every array once, DESIGN.md 4) over the sum of "
-                                 "their launch durations; SURVEY.md 8d's figure (per-instance atomics charged) beside it"
-                                 + ("; the deformation MLP's GEMMs are MFMA work: roofline_mlp" if deform else "")},
-            "roofline_check": {"all_fractions_le_1": not violations, "violations": violations or None},
-            "stages_ms": stages,
-            "stages_note": "hipEvent pairs around each launch (mgs_set_option('profile', 2)): a pair reads ~2 us longer than "
-                           "rocprofv3's kernel duration for the same launch, so their sum exceeds ms_per_step; the committed "
-                           "profiles/r06_rocprofv3_kernel_stats_*.csv carry the kernel durations",
         }
-        if not args.no_cpu_baseline and n_gpus == 1:
-            if deform:
-                out["cpu_baseline"] = cpu_baseline_dynamic(syn, sc, cam, d_color_h, d_feat_h, P, cfg.get("timesteps", 1),
-                                                           renders_total, args.cpu_seconds * 2)
+        if args.full:
+            out["config"].update({
+                "num_rendered_R": int(R), "R_over_P": R / (P * launch_views), "num_rendered_reference": int(R_reference),
+                "visible_gaussians_per_launch": nvis, "block_gaussian_incidences_per_launch": incidences,
+                "chunks_per_launch": chunks, "pixel_chunks_per_launch": pixel_chunks, "direct_binning": bool(direct)})
+            out.update({
+                "roofline": roof, "roofline_fwd": roof_fwd, "roofline_by_kernel": by_kernel,
+                "roofline_mlp": mlp_block,
+                "path_hbm": {"algorithmic_bytes_per_step_per_gpu": path_model,
+                             "kernel_ms_per_step_per_gpu": rast_ms,
+                             "achieved_GBps": (path_model / (rast_ms * 1e-3) / 1e9) if rast_ms > 0 else None,
+                             "frac_of_peak": path_frac,
+                             "counter_bytes_per_step_per_gpu": path_traffic,
+                             "frac_of_peak_by_counter_bytes": (path_traffic / (rast_ms * 1e-3) / 1e9 / HBM_PEAK_GBS)
+                             if path_traffic and rast_ms > 0 else None,
+                             "survey_8d_bytes_per_step_per_gpu": s8d_path,
+                             "note": "the rasterizer's kernels (five with the direct bucket-rank binning, six with a scatter "
+                                     "launch, seven with segment sort + merge): model bytes (every array once, DESIGN.md 4) "
+                                     "over the sum of their launch durations; SURVEY.md 8d's figure (per-instance atomics "
+                                     "charged) beside it"
+                                     + ("; the deformation MLP's GEMMs are MFMA work: roofline_mlp" if deform else "")},
+                "roofline_check": {"all_fractions_le_1": not violations, "violations": violations or None},
+                "stages_ms": stages,
+                "stages_note": "hipEvent pairs around each launch (mgs_set_option('profile', 2)): a pair reads ~2 us longer "
+                               "than rocprofv3's kernel duration for the same launch, so their sum exceeds ms_per_step; the "
+                               "committed profiles/r06_rocprofv3_kernel_stats_*.csv carry the kernel durations",
+            })
+            if not args.no_cpu_baseline and n_gpus == 1:
+                if deform:
+                    out["cpu_baseline"] = cpu_baseline_dynamic(syn, sc, cam, d_color_h, d_feat_h, P, cfg.get("timesteps", 1),
+                                                               renders_total, args.cpu_seconds * 2)
+                else:
+                    out["cpu_baseline"] = cpu_baseline(syn, sc, cam, d_color_h, d_feat_h, P, args.cpu_seconds)
+                    # SURVEY.md 8d's protocol: the same port on 8 threads and on 1 beside all the host's cores (~10 s each)
+                    out["cpu_baseline_threads8"] = cpu_baseline(syn, sc, cam, d_color_h, d_feat_h, P, args.cpu_seconds * 0.6,
+                                                                threads=8, max_passes=3)
+                    out["cpu_baseline_threads1"] = cpu_baseline(syn, sc, cam, d_color_h, d_feat_h, P, args.cpu_seconds * 0.6,
+                                                                threads=1, max_passes=2)
+                out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
             else:
-                out["cpu_baseline"] = cpu_baseline(syn, sc, cam, d_color_h, d_feat_h, P, args.cpu_seconds)
-                # SURVEY.md 8d's protocol: the same port on 8 threads and on 1 beside all the host's cores (bounded: ~10 s each)
-                out["cpu_baseline_threads8"] = cpu_baseline(syn, sc, cam, d_color_h, d_feat_h, P, args.cpu_seconds * 0.6,
-                                                            threads=8, max_passes=3)
-                out["cpu_baseline_threads1"] = cpu_baseline(syn, sc, cam, d_color_h, d_feat_h, P, args.cpu_seconds * 0.6,
-                                                            threads=1, max_passes=2)
-            out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
-        else:
-            out["cpu_baseline"] = None
-        if n_gpus == 1 and not deform and not args.no_reference_kernels:  # (independent of --no-cpu-baseline: it runs on the GPU)
-            out["reference_kernels_same_gpu"] = reference_kernels(syn, sc, cam, d_color_h, d_feat_h, P, F, value)
+                out["cpu_baseline"] = None
+            if n_gpus == 1 and not deform and not args.no_reference_kernels:  # (independent of --no-cpu-baseline: GPU)
+                out["reference_kernels_same_gpu"] = reference_kernels(syn, sc, cam, d_color_h, d_feat_h, P, F, value)
         # the LAST keys of the line are the ones a truncated tail still shows: what every mode measured, the package default
         # ("eager-safe": what an unmodified caller gets) first
         out["headline_mode"] = mode

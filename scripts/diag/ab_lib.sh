@@ -7,7 +7,7 @@ for v in "$@"; do
   if [ "$v" = shipped ]; then cp /tmp/shipped.so manigaussian_amd/libmgsplat.so; else cp .alt/libmgsplat_$v.so manigaussian_amd/libmgsplat.so; fi
   [ -n "$AB_NOTEST" ] || timeout 300 python -m pytest tests/test_binning.py tests/test_gpu_parity.py -x -q -m gpu -k "binning or golden or c3" -p no:cacheprovider > $out/pytest_$v.log 2>&1; [ -n "$AB_NOTEST" ] || { echo "$v pytest rc=$?"; tail -1 $out/pytest_$v.log; }
   for c in ${AB_CONFIGS:-ref16k c3}; do
-    timeout 200 python bench.py $( if [[ $c == views* ]]; then echo "--config c3 --views ${c#views}"; elif [[ $c == P* ]]; then echo "--config c3 --P ${c#P}"; else echo "--config $c"; fi ) --steps 300 --warmup 50 --mode eager-st --only-mode --no-cpu-baseline --no-reference-kernels > $out/bench_${v}_$c.json 2> $out/bench_${v}_$c.err
+    timeout 200 python bench.py --full $( if [[ $c == views* ]]; then echo "--config c3 --views ${c#views}"; elif [[ $c == P* ]]; then echo "--config c3 --P ${c#P}"; else echo "--config $c"; fi ) --steps 300 --warmup 50 --mode eager-st --only-mode --no-cpu-baseline --no-reference-kernels > $out/bench_${v}_$c.json 2> $out/bench_${v}_$c.err
     python - $out/bench_${v}_$c.json $v $c <<'P'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

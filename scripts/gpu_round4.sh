@@ -49,7 +49,7 @@ for W in tests quick exp host pmc bench configs stats stats_dyn variants trace; 
   host)
     timeout 300 python scripts/host_profile3.py > $OUT/host_profile.log 2>&1; echo "host rc=$?"; head -40 $OUT/host_profile.log ;;
   bench)
-    timeout 900 python bench.py --strict-roofline > $OUT/bench.log 2>&1; echo "bench rc=$?"
+    timeout 900 python bench.py --full --strict-roofline > $OUT/bench.log 2>&1; echo "bench rc=$?"
     tail -1 $OUT/bench.log > $OUT/bench.json; line < $OUT/bench.json
     timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_form.log 2>&1; echo "bench (driver form) rc=$?"
     tail -1 $OUT/bench_driver_form.log > $OUT/bench_driver_form.json; line < $OUT/bench_driver_form.json ;;
@@ -57,7 +57,7 @@ for W in tests quick exp host pmc bench configs stats stats_dyn variants trace; 
     for c in "--config c2" "--config c5shape" "--config ref16k" "--views 4" "--views 8" "--config c4 --steps 30 --warmup 10" "--config c5 --steps 20 --warmup 8"; do
       n=$(echo $c | tr -d ' -' ); n=${n#config}
       case "$c" in *"config c4"*|*"config c5 "*) cpu="" ;; *) cpu="--no-cpu-baseline" ;; esac
-      timeout 1200 python bench.py $c $cpu --strict-roofline > $OUT/bench_$n.log 2>&1; echo "bench $c rc=$?"
+      timeout 1200 python bench.py $c $cpu --full --strict-roofline > $OUT/bench_$n.log 2>&1; echo "bench $c rc=$?"
       tail -1 $OUT/bench_$n.log > $OUT/bench_$n.json; line < $OUT/bench_$n.json
     done ;;
   stats)

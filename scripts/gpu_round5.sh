@@ -47,7 +47,7 @@ for W in golden quick tests host pmc bench configs stats trace extra; do
   host)
     timeout 600 python scripts/host_profile5.py > $OUT/host_profile.log 2>&1; echo "host rc=$?"; grep -v "^$" $OUT/host_profile.log | head -60 ;;
   bench)
-    timeout 900 python bench.py --strict-roofline > $OUT/bench.log 2>&1; echo "bench rc=$?"
+    timeout 900 python bench.py --full --strict-roofline > $OUT/bench.log 2>&1; echo "bench rc=$?"
     tail -1 $OUT/bench.log > $OUT/bench.json; line < $OUT/bench.json
     timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_form.log 2>&1; echo "bench (driver form) rc=$?"
     tail -1 $OUT/bench_driver_form.log > $OUT/bench_driver_form.json; line < $OUT/bench_driver_form.json ;;
@@ -56,7 +56,7 @@ for W in golden quick tests host pmc bench configs stats trace extra; do
     for c in "${CFGS[@]}"; do
       n=$(echo $c | tr -d ' -' ); n=${n#config}
       case "$c" in *"config c4"*|*"config c5 "*) cpu="" ;; *) cpu="--no-cpu-baseline" ;; esac
-      timeout 1200 python bench.py $c $cpu --strict-roofline > $OUT/bench_$n.log 2>&1; echo "bench $c rc=$?"
+      timeout 1200 python bench.py $c $cpu --full --strict-roofline > $OUT/bench_$n.log 2>&1; echo "bench $c rc=$?"
       tail -1 $OUT/bench_$n.log > $OUT/bench_$n.json; line < $OUT/bench_$n.json
     done ;;
   stats)

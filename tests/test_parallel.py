@@ -304,7 +304,7 @@ def test_bench_self_launches_two_ranks_on_one_device():
     torch.distributed.run; --one-device --backend gloo are the testing flags (both ranks on cuda:0).  The JSON line must
     say 2 ranks, name both devices, and carry the all-reduce volume (the parameter gradients only: 55 floats/Gaussian)."""
     r, j = _bench(["--gpus", "2", "--one-device", "--backend", "gloo", "--steps", "20", "--warmup", "5", "--mode", "eager-st",
-                   "--only-mode", "--no-cpu-baseline", "--P", "20000"])
+                   "--only-mode", "--no-cpu-baseline", "--P", "20000", "--full"])
     assert r.returncode == 0 and j is not None, (r.stdout[-2000:], r.stderr[-3000:])
     assert j["n_gpus"] == 2 and j["distributed"]["world_size_seen"] == 2 and len(j["distributed"]["device_ids"]) == 2
     assert j["distributed"]["allreduce_bytes_per_step"] == 20000 * (3 + 1 + 12 + 3 + 4 + 32) * 4
@@ -365,7 +365,7 @@ def test_rccl_call_sequence_runs_on_one_device(cfg):
     process group of ONE rank and issues the exact call sequence to the device; not skipped on a one-GPU box.  What this
     proves: the calls are well-formed for RCCL on this stack (dtypes, contiguity, sizes, stream semantics, sub-groups); what
     it cannot: transport over xGMI."""
-    args = ["--dry-collectives", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-reference-kernels"]
+    args = ["--dry-collectives", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-reference-kernels", "--full"]
     if cfg == "c3":
         args += ["--P", "20000", "--mode", "graph"]  # all modes: graph replay with alternating buckets, eager, ...
     else:

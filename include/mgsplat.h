@@ -46,8 +46,8 @@ extern "C" {
 #define MGS_PENDING 2              /* mgs_forward_result: the device has not reported yet */
 #define MGS_RETRY_TABLE_INIT 3     /* mgs_forward_result (ABI v8): the preprocess launch's table hand-shake gave up (a workgroup
                                       made no progress for ~1 s): nothing was binned, the images are background only.  Run the
-                                      forward again on the same workspaces with opt.table_init = 1 (a blocking forward does that
-                                      by itself; an asynchronous one reports it here instead of a generic MGS_ERR_HIP) */
+                                      forward again on the same workspaces with opt.table_init = 1 (every blocking forward does
+                                      that by itself; an asynchronous one reports it here instead of a generic MGS_ERR_HIP) */
 
 #define MGS_MAX_FEATURE_CHANNELS 64
 
@@ -68,12 +68,20 @@ typedef struct MgsOptions {
   int32_t seg;          /* 2048*: keys per LDS-sorted segment (512, 1024, 2048, 4096: for lists of >> 8192 per tile)  */
   int32_t gm_waves;     /* 12*: render backward (one workgroup per CU): 12 waves x 168 registers, two pixels per step;
                            16 / 8: the one-pixel-per-step forms of rounds 2-4 (16 x 128 / 8 x 256 registers)            */
-  int32_t dbg;          /* 0*: diagnostics (256: phase timeline of the render forward, mgs_debug_read_trace; 512: test
-                           hook -- the table-zeroing workgroup of the forward preprocess sleeps ~0.3 ms first; 1024: test
-                           hook -- it never publishes the tables, the hand-shake gives up after ~1 s)                     */
+  int32_t dbg;          /* 0*: diagnostic bits, every one of them here (A/B switches and test hooks):
+                             256      phase timelines: render forward, render backward, bucket rank (mgs_debug_read_trace*)
+                             512      test hook: the table-zeroing workgroup of the forward preprocess sleeps ~0.3 ms first
+                             1024     test hook: it never publishes the tables, the hand-shake gives up after ~1 s
+                             2048     render backward: a block's chunks 4..7 go to waves 4..7 (default: 7..4)
+                             0x7000   bits 12-14 = 1 + log2 of the bucket rank's parts per tile (0: chosen by the tile count)
+                             32768    direct binning off: the bin scatter launch writes the tile keys
+                             1 << 16  render backward (12 waves): the extra chunks 8, 9 are not split between two waves
+                           512 and 1024 reach the forward preprocess only; a forward retried after a hand-shake give-up
+                           runs without them                                                                               */
   int32_t table_init;   /* 0*: the forward preprocess launch zeroes its own tile tables (workgroup 0 + a bounded hand-shake:
                            one launch fewer); 1: a zero-fill launch ahead of it -- no workgroup ever waits for another.
-                           debug = 1 implies 1; a blocking forward whose hand-shake gave up re-runs itself with 1           */
+                           debug = 1 implies 1; every blocking forward (fused with or without host_status, the two-call
+                           stage 1, the view batch) whose hand-shake gave up re-runs itself with 1                          */
 } MgsOptions;
 void mgs_options_default(MgsOptions* o);  /* fills every field, set = 1 */
 
@@ -156,7 +164,8 @@ size_t mgs_backward_scratch_bytes(int P, int M, int F);
  * (Gaussian, tile) instances of the reference's 3-sigma tile rects -- THE REFERENCE'S INTEGER (rasterizer_impl.cu:280-284),
  * whatever MgsOptions.tight_bins says (the instances actually binned are fewer under tight_bins = 1; the count is a safe
  * size for stage 2's workspace) -- this call synchronises the stream once, exactly where the reference does its blocking
- * cudaMemcpy (rasterizer_impl.cu:284). */
+ * cudaMemcpy (rasterizer_impl.cu:284).  If the preprocess's table hand-shake gave up (MGS_RETRY_TABLE_INIT), the call
+ * synchronises and runs the preprocess again with opt.table_init = 1 by itself. */
 int mgs_rasterize_forward_preprocess(const MgsRasterArgs* a, int32_t* radii, int32_t* num_rendered,
                                      mgs_stream_t stream);
 
@@ -181,7 +190,8 @@ int mgs_rasterize_forward_render(const MgsRasterArgs* a, int32_t num_rendered, c
  *     MGS_OK (images enqueued, *num_rendered set -- the reference's integer, see mgs_rasterize_forward_preprocess;
  *     mgs_forward_result reports the instances actually binned, which is what sizes a workspace) or MGS_NEED_CAPACITY
  *     (*num_rendered set, geom + radii valid, images NOT rendered: call mgs_rasterize_forward_render with a binning
- *     workspace of at least mgs_binning_bytes(*num_rendered, W, H, F)).
+ *     workspace of at least mgs_binning_bytes(*num_rendered, W, H, F)).  A table hand-shake that gave up is retried inside
+ *     the call with opt.table_init = 1, on either path (host_status or the blocking read-back).
  *     A chunk-pool overflow (only possible with a->chunk_pool != 0) is reported by mgs_forward_result.
  *   a->async_forward == 1: enqueues everything and returns MGS_OK at once with *num_rendered = -1: no host-device
  *     synchronisation at all (the call can be captured into a HIP graph together with its backward).  If the scene outgrew
@@ -224,7 +234,7 @@ int mgs_rasterize_backward(const MgsRasterArgs* a, int32_t num_rendered, const i
  * campos / tanfov fields are ignored); images are [V,3,H,W] / [V,F,H,W]; radii, dL_dmeans2D, dL_dconic are [V,P,.];
  * dL_dcolors is [V,P,3] with SH colours (colours differ per view) and [P,3] with colors_precomp; every other gradient is
  * per Gaussian, summed over the views on the device.  Workspaces are sized by the mgs_views_*_bytes functions.
- * host_status is required (see mgs_rasterize_forward; async_forward works the same).  Needs V <= 16 (any tile count; V * tiles <= 4096 keeps the
+ * host_status is required (see mgs_rasterize_forward; async_forward and the hand-shake retry work the same).  Needs V <= 16 (any tile count; V * tiles <= 4096 keeps the
  * binning tables in LDS). */
 typedef struct MgsView {
   float tanfovx, tanfovy;

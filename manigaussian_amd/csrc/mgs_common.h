@@ -224,10 +224,9 @@ struct Options {
   int exact_cull = 1;      // exact ellipse-vs-block cull on top of the bbox cull in the render forward
   int bin_mode = 2;        // 2: tables in LDS + ONE bucket-rank launch; 1: tables in LDS (up to LDS_TILES tiles) + segment sort + rank
                            // merge; 0: tables in memory + segment sort + rank merge (see mgs_binning.hip)
-  int rank_mode = 1;       // derived from bin_mode: 1 = bucket rank, 0 = segment sort + rank merge
   int seg = 2048;          // bin_mode 1: entries per LDS-sorted segment (512, 1024 or 2048)
   int gm_waves = 12;       // render backward at one workgroup per CU: 12 = 12 waves, two pixels per step; 16 / 8 = the one-pixel forms
-  int dbg = 0;             // see RenderArgs::dbg
+  int dbg = 0;             // diagnostic bits: the table at MgsOptions.dbg (include/mgsplat.h)
   int table_init = 0;      // 0: the preprocess launch zeroes its tables itself (workgroup 0 + hand-shake); 1: a zero-fill launch first
 };
 // process-wide DIAGNOSTIC state only (never results or layouts): stage timers
@@ -298,7 +297,7 @@ struct RenderArgs {
   // Instance ids are then "virtual": id = view * Pg + Gaussian.
   int V, Pg, Hv, Hp;
   int colors_per_view;  // 1: `colors` is indexed by the virtual id (SH colours, per view), 0: by the Gaussian
-  int dbg;  // timing experiments only (results invalid when non-zero); 256: phase timeline of the forward
+  int dbg;  // MgsOptions.dbg without the preprocess's test hooks 512 / 1024 (the table at MgsOptions.dbg, include/mgsplat.h)
   const float* bg;
   const float* colors;   // [P,3] colors_precomp or geom.rgb
   const float* feats;    // [P,F]

@@ -133,7 +133,7 @@ __global__ void __launch_bounds__(NW * 64, TWO ? 4 : 1) gm_bwd_kernel(RenderArgs
   int u_lo = 0, u_hi = 2;
   if constexpr (PAIR && NW == 12) {
     const uint32_t lcu = (uint32_t)__builtin_amdgcn_readfirstlane((int)lcmax);  // (wave_umax's result lives in a VGPR: say it is uniform)
-    if (!(r.dbg & 4096) && lcu > 8u && lcu <= 10u && w >= 8) {  // (workgroup- and wave-uniform)
+    if (!(r.dbg & (1 << 16)) && lcu > 8u && lcu <= 10u && w >= 8) {  // (workgroup- and wave-uniform)
       cw = 8 + ((w - 8) >> 1);
       u_lo = (w - 8) & 1;
       u_hi = u_lo + 1;

@@ -82,11 +82,12 @@ def _fill_args(a, *, P, D, M, F, W, H, tanfovx, tanfovy, scale_modifier, prefilt
 
 
 # ---- host-side caches: everything that is a pure function of the problem shape is computed once --------------------------------
-_SIZES = {}      # (P, M, W, H) -> (geom bytes, img bytes), both rounded up to 256
-_BIN_BYTES = {}  # (cap, pool, W, H, F) -> binning bytes
-_WORST = {}      # (P, W, H, F, safe_bytes) -> (cannot_overflow, cap_worst, pool_worst)
-_LAYOUTS = {}    # (P, M, F) -> (sizes, accum_bytes)
-_TEMPLATES = {}  # shape + settings scalars + options version -> bytes of a pre-filled MgsRasterArgs
+# (V: 0 for a single view, else the views of a batch -- the mgs_views_* size functions)
+_SIZES = {}      # (P, M, W, H, V) -> (geom bytes, img bytes), both rounded up to 256
+_BIN_BYTES = {}  # (cap, pool, W, H, F, V, P) -> binning bytes
+_WORST = {}      # (P, W, H, F, V, safe_bytes) -> (cannot_overflow, cap_worst, pool_worst, worst bytes)
+_LAYOUTS = {}    # (P, M, F, V, per-view colours) -> (sizes, accum_bytes)
+_TEMPLATES = {}  # shape + settings scalars + options version -> bytes of a pre-filled MgsRasterArgs (V is not in the struct)
 _EMPTY_U8 = {}   # device -> an empty uint8 tensor (placeholder for workspaces that live in another tensor's arena)
 _SPLIT_WORKSPACES = False  # testing: geom / img / binning as three allocations (guard bands behind each, tests/test_gpu_parity.py)
 
@@ -95,38 +96,44 @@ def _up256(n):
     return (n + 255) & ~255
 
 
-def _shape_sizes(L, P, M, W, H):
-    k = (P, M, W, H)
+def _shape_sizes(L, P, M, W, H, V):
+    k = (P, M, W, H, V)
     v = _SIZES.get(k)
     if v is None:
-        v = _SIZES[k] = (_up256(L.mgs_geom_bytes(P, M, W, H)), _up256(L.mgs_img_bytes(W, H)))
+        g, i = (L.mgs_views_geom_bytes(P, M, W, H, V), L.mgs_views_img_bytes(W, H, V)) if V else \
+            (L.mgs_geom_bytes(P, M, W, H), L.mgs_img_bytes(W, H))
+        v = _SIZES[k] = (_up256(g), _up256(i))
     return v
 
 
-def _bin_bytes(L, cap, pool, W, H, F, P=0):
+def _bin_bytes(L, cap, pool, W, H, F, V=0, P=0):
     """Bytes of the binning workspace; P > 0: plus the room in which the forward preprocess writes the tile keys itself (no bin
     scatter launch; include/mgsplat.h mgs_binning_direct_extra) where the library offers it for the shape."""
-    k = (cap, pool, W, H, F, P)
+    k = (cap, pool, W, H, F, V, P)
     v = _BIN_BYTES.get(k)
     if v is None:
         if len(_BIN_BYTES) > 4096:
             _BIN_BYTES.clear()
-        v = L.mgs_binning_bytes2(cap, pool, W, H, F)
+        v = L.mgs_views_binning_bytes2(cap, pool, W, H, F, V) if V else L.mgs_binning_bytes2(cap, pool, W, H, F)
         if P > 0:
-            extra = L.mgs_binning_direct_extra(P, 1, W, H)
+            extra = L.mgs_binning_direct_extra(P, V, W, H)
             v = _up256(v) + extra if extra else v
         _BIN_BYTES[k] = v
     return v
 
 
-def _worst_case(L, P, W, H, F, T, dev=None):
+def _worst_case(L, P, W, H, F, V, T, dev=None):
+    """(cannot_overflow, capacity, chunk pool, bytes) of the binning workspace that holds every Gaussian in every tile (T: the
+    tiles of all views).  cannot_overflow: it fits the budget."""
     budget = _state.safe_bytes(dev)
-    k = (P, W, H, F, budget)
+    k = (P, W, H, F, V, budget)
     v = _WORST.get(k)
     if v is None:
-        cap_worst = P * T  # every Gaussian in every tile
-        ok = cap_worst < (1 << 30) and L.mgs_binning_bytes2(cap_worst, 0, W, H, F) <= budget
-        v = _WORST[k] = (ok, cap_worst, L.mgs_chunk_pool_max(cap_worst, W, H) if ok else 0)
+        cap_worst = P * T
+        nbytes = _bin_bytes(L, cap_worst, 0, W, H, F, V) if cap_worst < (1 << 30) else 0  # (pool 0: the worst case's)
+        ok = 0 < nbytes <= budget
+        pool = 0 if not ok else L.mgs_views_chunk_pool_max(cap_worst, W, H, V) if V else L.mgs_chunk_pool_max(cap_worst, W, H)
+        v = _WORST[k] = (ok, cap_worst, pool, nbytes)
     return v
 
 
@@ -157,7 +164,7 @@ class ForwardHandle:
     def __init__(self, a, opts, pending, R, keep=None, views=None, outs=None):
         self.a, self.opts, self.pending, self.R = a, opts, pending, R
         self.keep = keep    # the tensors whose addresses `a` holds (converted / padded copies would otherwise be freed)
-        self.views = views  # (MgsView array, V) of a batched forward, else None
+        self.views = views  # (MgsView array, V, the camera tensors it points to) of a view batch, else None
         self.outs = outs    # weak references to (out_color, out_feature): a recovery re-renders into them if they still live
 
     def num_rendered_nowait(self) -> int:
@@ -240,7 +247,7 @@ def recover_forward(handle, radii, dev):
     if not handshake_only:
         R = max(int(p.num_rendered), 0)
         cap = R + R // 4 + 4096
-        nbytes = L.mgs_views_binning_bytes2(cap, 0, W, H, F, V) if V else L.mgs_binning_bytes2(cap, 0, W, H, F)
+        nbytes = _bin_bytes(L, cap, 0, W, H, F, V)
         binning = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     out_color = handle.outs[0]() if handle.outs and handle.outs[0] is not None else None
     out_feat = handle.outs[1]() if handle.outs and handle.outs[1] is not None else None
@@ -269,27 +276,31 @@ def recover_forward(handle, radii, dev):
     return R2
 
 
-def _grad_layout(L, P, M, F):
-    """Float offsets of the backward's single allocation: [scratch | dL_dcolors | dL_dfeature | means3D | opacity | sh |
+def _grad_layout(L, P, M, F, V, precomp=False):
+    """Float sizes of the backward's single allocation: [scratch | dL_dcolors | dL_dfeature | means3D | opacity | sh |
     scales | rotations | cov3D | means2D | pad].  The first three regions are the accumulators; the gradients of the
     Gaussian PARAMETERS (colours or SH, features, means, opacity, scales, rotations) are contiguous, so one all-reduce
-    over the span they cover (parallel.flat_alias) moves nothing else."""
-    k = (P, M, F)
+    over the span they cover (parallel.flat_alias) moves nothing else.  A batch of V views has V x P means2D rows and,
+    unless its colours are precomputed (precomp: one per Gaussian), V x P colour rows."""
+    k = (P, M, F, V, precomp and V > 0)
     v = _LAYOUTS.get(k)
     if v is None:
-        scratch_f = (L.mgs_backward_scratch_bytes(P, M, F) + 3) // 4
-        sizes = [scratch_f, 3 * P, F * P, 3 * P, P, 3 * M * P, 3 * P, 4 * P, 6 * P, 3 * P, 4]
-        accum_bytes = ((scratch_f + 3 * P + F * P) * 4 + 15) // 16 * 16  # may reach into the next, fully rewritten, region
+        scratch = L.mgs_views_backward_scratch_bytes(P, M, F, V) if V else L.mgs_backward_scratch_bytes(P, M, F)
+        scratch_f = (scratch + 3) // 4
+        n = max(V, 1) * P  # (view, Gaussian) pairs
+        ncol = P if precomp else n
+        sizes = [scratch_f, 3 * ncol, F * P, 3 * P, P, 3 * M * P, 3 * P, 4 * P, 6 * P, 3 * n, 4]
+        accum_bytes = ((scratch_f + 3 * ncol + F * P) * 4 + 15) // 16 * 16  # may reach into the next, fully rewritten, region
         v = _LAYOUTS[k] = (sizes, accum_bytes)
     return v
 
 
-def _grad_offsets(L, P, M, F):
+def _grad_offsets(L, P, M, F, V, precomp=False):
     """(float offsets of the regions of _grad_layout, total floats)."""
-    k = (P, M, F, "offs")
+    k = (P, M, F, V, precomp and V > 0, "offs")
     v = _LAYOUTS.get(k)
     if v is None:
-        sizes, _ = _grad_layout(L, P, M, F)
+        sizes, _ = _grad_layout(L, P, M, F, V, precomp)
         offs, o = [], 0
         for n in sizes:
             offs.append(o)
@@ -336,10 +347,11 @@ def rasterize_gaussians(background, means3D, colors, language_feature, opacity, 
 
 def _forward(background, means3D, colors, language_feature, opacity, scales, rotations, scale_modifier, cov3D_precomp,
              viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered,
-             debug, include_feature, want_grad_buffer, blocking=False):
+             debug, include_feature, want_grad_buffer, blocking=False, views=None):
     """rasterize_gaussians + (want_grad_buffer) the backward's allocation, whose accumulator block the forward's
     preprocess kernel zeroes on the side: returns (ForwardHandle or int, color, feature, radii, geom, binning, img,
-    grad_buffer or None)."""
+    grad_buffer or None).  views = (MgsView array, V, the camera tensors it points to): V views of the one Gaussian set in
+    one call (manigaussian_amd/views.py; the camera arguments are unused): color [V,3,H,W], feature [V,F,H,W], radii [V,P]."""
     L = _lib.lib()
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:59-61
@@ -347,6 +359,8 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
         raise RuntimeError("diff_gaussian_rasterization (MI355X build) needs tensors on a HIP device; "
                            "there is no CPU path")
     dev = means3D.device
+    V = views[1] if views is not None else 0
+    lead = (V,) if V else ()
     P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
     means3D = _f32c(means3D, "means3D", dev)
     background = _f32c(background, "background", dev)
@@ -375,11 +389,11 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
     with _on_device(dev):
         u8 = dict(dtype=torch.uint8, device=dev)
         if P == 0:  # rasterize_points.cu:92: empty workspaces, zero images
-            out_color = torch.zeros((3, H, W), dtype=_F32, device=dev)
-            out_feat = torch.zeros((F_user, H, W) if include_feature else (1,), dtype=_F32, device=dev)
+            out_color = torch.zeros(lead + (3, H, W), dtype=_F32, device=dev)
+            out_feat = torch.zeros(lead + (F_user, H, W) if include_feature else (1,), dtype=_F32, device=dev)
             e = torch.empty((0,), **u8)
-            return (0, out_color, out_feat, torch.zeros((0,), dtype=torch.int32, device=dev), e, e.clone(), e.clone(),
-                    None)
+            return (0, out_color, out_feat, torch.zeros(lead + (0,), dtype=torch.int32, device=dev), e, e.clone(),
+                    e.clone(), None)
         st = _state.device_state(dev)
         capturing = _capturing()
         if not capturing:
@@ -387,12 +401,12 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
         # everything that is a function of the shape alone comes from caches (sizes, the pre-filled argument struct)
         tmpl, opts = _template(P, int(degree), M, F, W, H, float(tan_fovx), float(tan_fovy), float(scale_modifier),
                                bool(prefiltered), bool(debug), include_feature)
-        key = (P, W, H, F, opts["tight_bins"])
-        T = ((W + 15) // 16) * ((H + 15) // 16)
-        cannot_overflow, cap_worst, pool_worst = _worst_case(L, P, W, H, F, T, dev)
+        # (the marks key of a batch is parsed by the compiled binding's marks store: csrc/mgs_torch.cpp Key)
+        key = ("views", V, P, W, H, F, opts["tight_bins"]) if V else (P, W, H, F, opts["tight_bins"])
+        T = max(V, 1) * ((W + 15) // 16) * ((H + 15) // 16)  # the tiles binned: those of every view
+        cannot_overflow, cap_worst, pool_worst, worst_bytes = _worst_case(L, P, W, H, F, V, T, dev)
         # ... charged against what live forwards of this device already hold (a node keeps its workspace until its backward):
         # V forwards before the first backward take the worst case only while the SUM fits, the rest go by their marks
-        worst_bytes = _bin_bytes(L, cap_worst, pool_worst, W, H, F) if cannot_overflow else 0
         if cannot_overflow and not blocking and _state.forward_mode() != "async" and \
                 not _state.worst_case_fits(st.index, worst_bytes, dev):
             cannot_overflow = False
@@ -401,47 +415,49 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
         lazy = (guess is not None and not blocking and not debug and not prefiltered and
                 _state.lazy_allowed(cannot_overflow))
         if capturing and not lazy:
-            raise RuntimeError("capturing a rasterizer forward into a HIP graph needs the asynchronous path: "
+            raise RuntimeError("capturing a rasterizer forward or a view batch into a HIP graph needs the asynchronous path: "
                                "manigaussian_amd.set_forward_mode('async'), then run this shape eagerly (twice) first so that "
                                "its workspace sizes are known, with debug=False")
-        if lazy:
-            cap, pool = guess
-        else:  # blocking path: the chunk pool is the worst case for the capacity (cannot overflow)
-            m = st.marks.get(key)
-            cap, pool = (m[0] + m[0] // 4 + 4096 if m else 4 * P + 4096), 0
         # ONE allocation for the three opaque workspaces [geom | img | binning] (each a multiple of 256 bytes), one for the
-        # two images; radii and the backward's gradient buffer have lifetimes of their own
-        gb, ib = _shape_sizes(L, P, M, W, H)
-        # (room for the keys of the direct binning: a worst-case capacity covers them by itself, and the blocking path's carving
-        #  is derived from the byte count -- extra bytes would only raise its capacity)
-        bb = _bin_bytes(L, cap, pool, W, H, F, P if lazy and cap != cap_worst else 0)
-        if _SPLIT_WORKSPACES:
-            ws3 = (torch.empty((gb,), **u8), torch.empty((ib,), **u8), torch.empty((bb,), **u8))
-            p_geom, p_img, p_bin = ws3[0].data_ptr(), ws3[1].data_ptr(), ws3[2].data_ptr()
-            ws = None
-        else:
+        # images; radii and the backward's gradient buffer have lifetimes of their own
+        gb, ib = _shape_sizes(L, P, M, W, H, V)
+        while True:
+            if lazy:
+                cap, pool = guess
+            else:  # waiting path: the chunk pool is the worst case for the capacity (cannot overflow)
+                m = st.marks.get(key)
+                cap, pool = (m[0] + m[0] // 4 + 4096 if m else 4 * max(V, 1) * P + 4096), 0
+            # The blocking path of a single view leaves binning_capacity at 0: the library then derives the carving from the
+            # buffer's BYTE COUNT, which is all a caller of the reference-shaped pair rasterize_gaussians /
+            # rasterize_gaussians_backward(R: int, binningBuffer) hands back -- forward and backward agree by construction.  The
+            # asynchronous path and a batch name (capacity, pool); the backward reuses this very struct (ForwardHandle.a).
+            named = lazy or V > 0
+            # (room for the keys of the direct binning where the capacity is named: a worst-case capacity covers them itself)
+            bb = _bin_bytes(L, cap, pool, W, H, F, V, P if named and cap != cap_worst else 0)
             try:
-                ws = torch.empty((gb + ib + bb,), **u8)
+                if _SPLIT_WORKSPACES:
+                    ws = [torch.empty((n,), **u8) for n in (gb, ib, bb)]
+                    p_geom, p_img, p_bin = (t.data_ptr() for t in ws)
+                else:
+                    ws = [torch.empty((gb + ib + bb,), **u8)]
+                    p_geom = ws[0].data_ptr()
+                    p_img, p_bin = p_geom + gb, p_geom + gb + ib
+                break
             except torch.cuda.OutOfMemoryError:
                 if not (lazy and cannot_overflow) or capturing:
                     raise
                 # the allocator cannot give the worst case: this forward goes by its marks and waits for the preprocess
                 lazy, cannot_overflow = False, False
-                m = st.marks.get(key)
-                cap, pool = (m[0] + m[0] // 4 + 4096 if m else 4 * P + 4096), 0
-                bb = _bin_bytes(L, cap, pool, W, H, F)
-                ws = torch.empty((gb + ib + bb,), **u8)
-            if lazy and cannot_overflow and want_grad_buffer:
-                _state.hold(st.index, worst_bytes, ws)
-            p_geom = ws.data_ptr()
-            p_img, p_bin = p_geom + gb, p_geom + gb + ib
-        if include_feature:
+        if lazy and cannot_overflow and want_grad_buffer:
+            _state.hold(st.index, worst_bytes, ws[-1])
+        if include_feature and not V:
             out = torch.empty((3 + F, H, W), dtype=_F32, device=dev)
             out_color, out_feat = out[:3], out[3:]
         else:
-            out_color = torch.empty((3, H, W), dtype=_F32, device=dev)
-            out_feat = torch.zeros((1,), dtype=_F32, device=dev)
-        radii = torch.empty((P,), dtype=torch.int32, device=dev)  # written for every Gaussian by the preprocess
+            out_color = torch.empty(lead + (3, H, W), dtype=_F32, device=dev)
+            out_feat = (torch.empty((V, F, H, W), dtype=_F32, device=dev) if include_feature else
+                        torch.zeros((1,), dtype=_F32, device=dev))
+        radii = torch.empty(lead + (P,), dtype=torch.int32, device=dev)  # written for every Gaussian by the preprocess
         a = _lib.MgsRasterArgs.from_buffer_copy(tmpl)
         a.background, a.means3D, a.shs, a.colors_precomp = _ptr(background), means3D.data_ptr(), _ptr(sh), _ptr(colors)
         a.language_feature = language_feature.data_ptr() if include_feature else None
@@ -452,55 +468,56 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
         m_ = st.marks.get(key)
         if m_ is not None:
             _lib.auto_seg(a, opts, m_[0], T)
-        slot_ptr, tag = st.take_slot()
-        # The blocking path leaves binning_capacity at 0: the library then derives the carving from the buffer's BYTE COUNT,
-        # which is all a caller of the reference-shaped pair rasterize_gaussians / rasterize_gaussians_backward(R: int,
-        # binningBuffer) hands back -- forward and backward agree by construction.  The asynchronous path names (capacity,
-        # pool) explicitly and its backward reuses this very struct (ForwardHandle.a).
-        if lazy:
-            a.binning_capacity, a.chunk_pool, a.status_tag, a.async_forward = cap, pool, tag, 1
-        else:
-            a.status_tag = tag
+        slot_ptr, a.status_tag = st.take_slot()
+        if named:
+            a.binning_capacity, a.chunk_pool, a.async_forward = cap, pool, int(lazy)
         grad_buffer = None
         if want_grad_buffer:
-            sizes, accum_bytes = _grad_layout(L, P, M, F)
+            sizes, accum_bytes = _grad_layout(L, P, M, F, V, colors.numel() != 0)
             grad_buffer = torch.empty((sum(sizes),), dtype=_F32, device=dev)
             a.bwd_accum, a.bwd_accum_bytes = grad_buffer.data_ptr(), accum_bytes
         stream = _stream(dev)
-        feat_ptr = out_feat.data_ptr() if include_feature else None
-        rc, R = _launch_forward(L, a, None, radii, out_color, out_feat, slot_ptr, stream)
-        pending = None
-        binning2 = None
-        if rc == _lib.MGS_NEED_CAPACITY:  # (waiting path) first call for this shape, or the scene grew: bin + render again
+        what = "rasterize views" if V else "rasterize_gaussians"
+        rc, R = _launch_forward(L, a, views, radii, out_color, out_feat, slot_ptr, stream)
+        pending = binning2 = None
+        while rc == _lib.MGS_NEED_CAPACITY:  # (waiting path) first call for this shape, or the scene grew: bin + render again
+            st.learn(key, _binned_now(slot_ptr))  # the marks hold BINNED counts (advisor r4: not the 3-sigma-rect count R)
             cap = R + R // 4 + 4096  # (R: the reference's 3-sigma-rect count, at least the instances binned)
-            binning2 = torch.empty((L.mgs_binning_bytes2(cap, 0, W, H, F),), **u8)
-            a.binning, a.binning_bytes, a.binning_capacity, a.chunk_pool = binning2.data_ptr(), binning2.numel(), 0, 0
-            rc = L.mgs_rasterize_forward_render(ctypes.byref(a), R, radii.data_ptr(), out_color.data_ptr(), feat_ptr,
-                                                stream)
-            _lib.check(rc, "rasterize_gaussians")
-            st.learn(key, _binned_now(slot_ptr))  # the marks hold BINNED counts (advisor r4: not the 3-sigma-rect count)
+            binning2 = torch.empty((_bin_bytes(L, cap, 0, W, H, F, V, P if named else 0),), **u8)
+            a.binning, a.binning_bytes = binning2.data_ptr(), binning2.numel()
+            if not V:
+                feat_ptr = out_feat.data_ptr() if include_feature else None
+                _lib.check(L.mgs_rasterize_forward_render(ctypes.byref(a), R, radii.data_ptr(), out_color.data_ptr(),
+                                                          feat_ptr, stream), what)
+                break
+            # the ABI has no render-only entry for a batch: the whole batch runs again, with room for R
+            a.binning_capacity = cap
+            _lib.fill_options(a, opts)
+            _lib.auto_seg(a, opts, st.marks.get(key)[0], T)
+            slot_ptr, a.status_tag = st.take_slot()
+            rc, R = _launch_forward(L, a, views, radii, out_color, out_feat, slot_ptr, stream)
         else:
-            _lib.check(rc, "rasterize_gaussians")
+            _lib.check(rc, what)
             # a forward that a backward will follow can be repaired there if it overflowed (recover_forward)
             # (the marks are learned from the device's report -- the instances actually binned --, not from the blocking
             #  call's return value, which is the reference's 3-sigma-rect count)
-            pending = _state.Pending(a, 0, slot_ptr, key, captured=capturing, recoverable=want_grad_buffer and not capturing)
+            pending = _state.Pending(a, V, slot_ptr, key, captured=capturing, recoverable=want_grad_buffer and not capturing)
             st.add(pending)  # captured forwards report at every replay: _state.check_status()
         handle = ForwardHandle(a, opts, pending, R, (background, means3D, sh, colors, language_feature, opacity, scales,
                                                      rotations, cov3D_precomp, viewmatrix, projmatrix, campos),
-                               outs=(_weak(out_color), _weak(out_feat) if include_feature and F == F_user else None))
-        if ws is None:
-            geom, img, binning = ws3[0], ws3[1], (binning2 if binning2 is not None else ws3[2])
+                               views=views, outs=(_weak(out_color), _weak(out_feat) if include_feature and F == F_user else None))
+        if _SPLIT_WORKSPACES:
+            geom, img, binning = ws[0], ws[1], (binning2 if binning2 is not None else ws[2])
         elif blocking:  # the reference-shaped triple: three tensors whose byte counts describe their carving
-            geom, img = ws[:gb], ws[gb:gb + ib]
-            binning = binning2 if binning2 is not None else ws[gb + ib:]
+            geom, img = ws[0][:gb], ws[0][gb:gb + ib]
+            binning = binning2 if binning2 is not None else ws[0][gb + ib:]
         else:         # the autograd path keeps ONE tensor alive (the backward reads the addresses from the handle)
             e = _EMPTY_U8.get(dev)
             if e is None:
                 e = _EMPTY_U8[dev] = torch.empty((0,), **u8)
-            geom, img, binning = ws, e, (binning2 if binning2 is not None else e)
+            geom, img, binning = ws[0], e, (binning2 if binning2 is not None else e)
     if include_feature and F != F_user:
-        out_feat = out_feat[:F_user].contiguous()
+        out_feat = out_feat[..., :F_user, :, :].contiguous()
     return handle, out_color, out_feat, radii, geom, binning, img, grad_buffer
 
 
@@ -548,11 +565,12 @@ def _backward(background, means3D, radii, colors, language_feature, scales, rota
               geomBuffer, R, binningBuffer, imageBuffer, debug, include_feature, grad_buffer):
     """rasterize_gaussians_backward; grad_buffer = the allocation _forward() handed out (accumulators already
     zeroed by the forward's preprocess kernel) or None.  R: the forward's ForwardHandle (its MgsRasterArgs is reused;
-    the count may still be unknown) or the count as an int (buffers sized by mgs_binning_bytes)."""
+    the count may still be unknown) or the count as an int (buffers sized by mgs_binning_bytes).  The handle of a view
+    batch's forward (handle.views) takes cotangents [V,3,H,W] / [V,F,H,W] and gives dL_dmeans2D [V,P,3]."""
     L = _lib.lib()
     dev = means3D.device
     P = int(means3D.size(0))
-    H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
+    H, W = int(dL_dout_color.size(-2)), int(dL_dout_color.size(-1))
     M = int(sh.size(1)) if sh.numel() != 0 else 0
     include_feature = bool(include_feature)
     dL_dout_color = _f32c(dL_dout_color, "dL_dout_color", dev)
@@ -562,9 +580,10 @@ def _backward(background, means3D, radii, colors, language_feature, scales, rota
         F = _padded_F(F_user)
         dL_dout_language_feature = _f32c(dL_dout_language_feature, "dL_dout_language_feature", dev)
         if F != F_user:
-            dL_dout_language_feature = torch.cat(
-                [dL_dout_language_feature, dL_dout_language_feature.new_zeros((F - F_user, H, W))], 0)
+            g = dL_dout_language_feature
+            dL_dout_language_feature = torch.cat([g, g.new_zeros(g.shape[:-3] + (F - F_user, H, W))], -3)
     handle = R if isinstance(R, ForwardHandle) else None
+    V = handle.views[1] if handle is not None and handle.views is not None else 0
     keep = None
     with _on_device(dev):
         if P == 0:
@@ -575,7 +594,8 @@ def _backward(background, means3D, radii, colors, language_feature, scales, rota
         # accumulates into (acc8 | dL_dcolors | dL_dfeature) come first and are contiguous, so the library zeroes
         # them with a single fill; everything else is fully written by the kernels.  Regions are addressed by offset
         # (no split / view tensors on the way in; one as_strided per gradient on the way out).
-        (o_scr, o_col, o_feat, o_m3, o_op, o_sh, o_sc, o_rot, o_cov, o_m2, _o_pad), total = _grad_offsets(L, P, M, F)
+        (o_scr, o_col, o_feat, o_m3, o_op, o_sh, o_sc, o_rot, o_cov, o_m2, _o_pad), total = \
+            _grad_offsets(L, P, M, F, V, colors.numel() != 0)
         prezeroed = grad_buffer is not None and grad_buffer.numel() == total
         flat = grad_buffer if prezeroed else torch.empty((total,), dtype=_F32, device=dev)
         base = flat.data_ptr()
@@ -607,16 +627,20 @@ def _backward(background, means3D, radii, colors, language_feature, scales, rota
             _lib.fill_options(a)
             count = int(R)
         a.accum_prezeroed = 1 if prezeroed else 0
-        _lib.check(L.mgs_rasterize_backward(
-            ctypes.byref(a), count, radii.data_ptr(), dL_dout_color.data_ptr(),
-            _ptr(dL_dout_language_feature) if include_feature else None, base + 4 * o_m2, None,
-            base + 4 * o_op, base + 4 * o_col, (base + 4 * o_feat) if include_feature else None,
-            base + 4 * o_m3, base + 4 * o_cov, (base + 4 * o_sh) if M else None, base + 4 * o_sc, base + 4 * o_rot,
-            base + 4 * o_scr, (o_col - o_scr) * 4, _stream(dev)), "rasterize_gaussians_backward")
+        args = (count, radii.data_ptr(), dL_dout_color.data_ptr(),
+                _ptr(dL_dout_language_feature) if include_feature else None, base + 4 * o_m2, None,
+                base + 4 * o_op, base + 4 * o_col, (base + 4 * o_feat) if include_feature else None,
+                base + 4 * o_m3, base + 4 * o_cov, (base + 4 * o_sh) if M else None, base + 4 * o_sc, base + 4 * o_rot,
+                base + 4 * o_scr, (o_col - o_scr) * 4, _stream(dev))
+        if V:
+            _lib.check(L.mgs_rasterize_backward_views(ctypes.byref(a), V, handle.views[0], *args), "rasterize views (backward)")
+        else:
+            _lib.check(L.mgs_rasterize_backward(ctypes.byref(a), *args), "rasterize_gaussians_backward")
         view = flat.as_strided
+        g_m2 = view((V, P, 3), (3 * P, 3, 1), o_m2) if V else view((P, 3), (3, 1), o_m2)
         g_feat = view((P, F), (F, 1), o_feat) if include_feature else torch.zeros((1,), dtype=_F32, device=dev)
         g_sh = view((P, M, 3), (3 * M, 3, 1), o_sh) if M else flat.new_empty((P, 0, 3))
-        out = (view((P, 3), (3, 1), o_m2), view((P, 3), (3, 1), o_col), g_feat, view((P, 1), (1, 1), o_op),
+        out = (g_m2, view((P, 3), (3, 1), o_col), g_feat, view((P, 1), (1, 1), o_op),
                view((P, 3), (3, 1), o_m3), view((P, 6), (6, 1), o_cov), g_sh, view((P, 3), (3, 1), o_sc),
                view((P, 4), (4, 1), o_rot))
     del keep

@@ -67,7 +67,8 @@ struct Counters {
 };
 Counters& counters() { static Counters c; return c; }
 
-// shape key of the workspace marks: V = 0 single view (this file), V >= 1 a batch of V views (manigaussian_amd/views.py)
+// shape key of the workspace marks: V = 0 single view (this file and manigaussian_amd/_C.py), V >= 1 a batch of V views
+// (manigaussian_amd/_C.py _forward, key ("views", V, P, W, H, F, tight_bins))
 struct Key {
   int32_t V, P, W, H, F, tight;
   bool operator==(const Key& o) const { return V == o.V && P == o.P && W == o.W && H == o.H && F == o.F && tight == o.tight; }

@@ -133,6 +133,17 @@ def _or_empty(t):
     return _EMPTY if t is None else t
 
 
+def _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp):
+    """GaussianRasterizer's and GaussianRasterizerBatch's exclusivity rules; messages kept verbatim (typo included) from the
+    reference, __init__.py:202,205."""
+    if (shs is None) == (colors_precomp is None):
+        raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+    has_sr = scales is not None and rotations is not None
+    any_sr = scales is not None or rotations is not None
+    if (not has_sr and cov3D_precomp is None) or (any_sr and cov3D_precomp is not None):
+        raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+
+
 class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings):
         super().__init__()
@@ -145,13 +156,7 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, language_feature_precomp=None,
                 scales=None, rotations=None, cov3D_precomp=None):
-        # messages kept verbatim (typo included) from the reference, __init__.py:202,205
-        if (shs is None) == (colors_precomp is None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-        has_sr = scales is not None and rotations is not None
-        any_sr = scales is not None or rotations is not None
-        if (not has_sr and cov3D_precomp is None) or (any_sr and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+        _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
         return rasterize_gaussians(means3D, means2D, _or_empty(shs), _or_empty(colors_precomp),
                                    _or_empty(language_feature_precomp), opacities, _or_empty(scales),
                                    _or_empty(rotations), _or_empty(cov3D_precomp), self.raster_settings)

@@ -8,6 +8,7 @@ reference as well: RAST/cuda_rasterizer/backward.cu:541-590)."""
 import glob
 import os
 import types
+import warnings
 
 import numpy as np
 import pytest
@@ -1232,6 +1233,66 @@ def test_view_batch_workspaces_are_not_overrun(P, V, W, monkeypatch):
     gt.check()
     assert len(gt.bases) >= n_ws + 3
     assert torch.equal(ch, cb[0]) and torch.equal(rh, rb[0])
+
+
+class _RefusingTorch:
+    """Stand-in for the `torch` module inside manigaussian_amd._C whose allocator refuses uint8 requests of ONE size (the
+    worst-case workspace of the shape under test) with OutOfMemoryError: a Python exception, nothing reaches the device."""
+
+    def __init__(self, nbytes):
+        self.nbytes, self.refused = nbytes, 0
+
+    def __getattr__(self, name):
+        return getattr(torch, name)
+
+    def empty(self, size, *a, **kw):
+        n = int(size[0]) if isinstance(size, (tuple, list)) else int(size)
+        if kw.get("dtype") is torch.uint8 and n == self.nbytes:
+            self.refused += 1
+            raise torch.cuda.OutOfMemoryError("refused by the test")
+        return torch.empty(size, *a, **kw)
+
+
+@pytest.mark.parametrize("V", [0, 3], ids=["single_view", "3_views"])
+def test_worst_case_workspace_the_allocator_refuses_falls_back_to_the_marks(V, monkeypatch):
+    """A forward whose worst-case workspace the allocator refuses goes by the marks and waits for its preprocess, for a single
+    view (ctypes shim) and a view batch alike: no warning, no error, the images and radii of a blocking-mode run bit for bit
+    and its gradients to float-atomic order."""
+    from manigaussian_amd import _C, _state
+    dev = torch.device("cuda:0")
+    P, F, W, n = 3000, 32, 64, max(V, 1)
+    sc, cams, dC, dF = _batch_case(P, F, n, W, W)
+    bg = (0.1, 0.2, 0.3)
+
+    def run():
+        if V:
+            c, f, r, g, m2g = _run_batch(sc, cams, dC, dF, bg)
+            return c, f, r, dict(g, means2D=m2g)
+        with _C.use_compiled(False):
+            return util.run_hip(sc, cams[0], dC[0], dF[0], 1, True, bg)
+
+    L = _lib.lib()
+    gb, ib = _C._shape_sizes(L, P, 4, W, W, V)
+    ok, cap, pool, _ = _C._worst_case(L, P, W, W, F, V, n * ((W + 15) // 16) ** 2, dev)
+    assert ok, "the shape's worst case must fit the budget"
+    refusing = _RefusingTorch(gb + ib + _C._bin_bytes(L, cap, pool, W, W, F, V))
+    old_mode = _state.set_forward_mode("blocking")
+    try:
+        ref = run()
+        _state.set_forward_mode("safe")
+        monkeypatch.setattr(_C, "torch", refusing)
+        with warnings.catch_warnings():
+            warnings.simplefilter("error")
+            got = run()
+            _state.check_status(dev)
+    finally:
+        _state.set_forward_mode(old_mode)
+    assert refusing.refused >= 1, "the forward did not ask for its worst-case workspace"
+    (c0, f0, r0, g0), (c1, f1, r1, g1) = ref, got
+    assert torch.equal(c1, c0) and torch.equal(f1, f0) and torch.equal(r1, r0)
+    assert g1.keys() == g0.keys()
+    for k in g0:
+        assert (g1[k] - g0[k]).abs().max().item() <= 2e-5 * g0[k].abs().max().item() + 1e-12, k
 
 
 def _batch_case(P, F, V, W, H, seed=2, precomp=False):

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 8
+#define MGS_ABI_VERSION 9
 
 /* error codes */
 #define MGS_OK 0
@@ -257,6 +257,27 @@ int mgs_rasterize_backward_views(const MgsRasterArgs* a, int32_t V, const MgsVie
                                  float* dL_dmeans2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolors,
                                  float* dL_dfeature, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
                                  float* dL_drotations, void* scratch, size_t scratch_bytes, mgs_stream_t stream);
+
+/* ---- set batches (ABI v9): V views of S Gaussian sets of one size in one call.  ManiGaussian's training step renders the
+ * current frame and the deformed next frame, two sets (MG/neural_rendering.py:283,324).  a->P is the number of Gaussians PER SET;
+ * every attribute pointer of `a` is [S,P,.] (sets stacked along the leading dimension), view v renders set view_set[v]
+ * (host array of V ints, 0 <= view_set[v] < S <= 16; a set no view renders is allowed).  Images, radii, dL_dmeans2D,
+ * dL_dconic and, with SH colours, dL_dcolors are per view as in a view batch; every other gradient is [S,P,.]: row (s, i) sums
+ * the views of set s, rows of a set no view renders are zero.  Each view's image and radii are those of a single-view call on
+ * its set, bit for bit.  Workspaces are a V-view batch's (mgs_views_*_bytes, mgs_binning_direct_extra(P, V, ..));
+ * mgs_forward_result_views reads the status words.  The accumulator block (bwd_accum) is acc8 | dL_dcolors | dL_dfeature
+ * with S x P rows for dL_dfeature and, with colors_precomp, for dL_dcolors.  With S = 1 and every view on set 0 this is
+ * mgs_rasterize_forward_views / mgs_rasterize_backward_views. */
+size_t mgs_sets_backward_scratch_bytes(int P, int M, int F, int V, int S);
+int mgs_rasterize_forward_sets(const MgsRasterArgs* a, int32_t V, const MgsView* views, int32_t S, const int32_t* view_set,
+                               int32_t* radii, float* out_color, float* out_feature, int32_t* num_rendered,
+                               uint64_t* host_status, mgs_stream_t stream);
+int mgs_rasterize_backward_sets(const MgsRasterArgs* a, int32_t V, const MgsView* views, int32_t S, const int32_t* view_set,
+                                int32_t num_rendered, const int32_t* radii, const float* dL_dout_color,
+                                const float* dL_dout_feature, float* dL_dmeans2D, float* dL_dconic, float* dL_dopacity,
+                                float* dL_dcolors, float* dL_dfeature, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
+                                float* dL_dscales, float* dL_drotations, void* scratch, size_t scratch_bytes,
+                                mgs_stream_t stream);
 
 /* Replaces Rasterizer::markVisible (rasterizer_impl.cu:141-153).  present: uint8 [P] (torch.bool). */
 int mgs_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,

@@ -46,6 +46,11 @@ def _aligned16(t):
     return t if (t.numel() == 0 or t.data_ptr() % 16 == 0) else t.clone()
 
 
+def _sh_coeffs(sh, S):
+    """SH coefficients per Gaussian: sh is [P,M,3], or [S,P,M,3] in a batch of S Gaussian sets (S > 0)."""
+    return int(sh.size(2 if S else 1)) if sh.numel() != 0 else 0
+
+
 def _stream(dev):
     return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device()))
 
@@ -86,7 +91,7 @@ def _fill_args(a, *, P, D, M, F, W, H, tanfovx, tanfovy, scale_modifier, prefilt
 _SIZES = {}      # (P, M, W, H, V) -> (geom bytes, img bytes), both rounded up to 256
 _BIN_BYTES = {}  # (cap, pool, W, H, F, V, P) -> binning bytes
 _WORST = {}      # (P, W, H, F, V, safe_bytes) -> (cannot_overflow, cap_worst, pool_worst, worst bytes)
-_LAYOUTS = {}    # (P, M, F, V, per-view colours) -> (sizes, accum_bytes)
+_LAYOUTS = {}    # (P, M, F, V, per-view colours, S) -> (sizes, accum_bytes)
 _TEMPLATES = {}  # shape + settings scalars + options version -> bytes of a pre-filled MgsRasterArgs (V is not in the struct)
 _EMPTY_U8 = {}   # device -> an empty uint8 tensor (placeholder for workspaces that live in another tensor's arena)
 _SPLIT_WORKSPACES = False  # testing: geom / img / binning as three allocations (guard bands behind each, tests/test_gpu_parity.py)
@@ -159,13 +164,14 @@ class ForwardHandle:
     the pending device report.  int(handle) blocks until the instance count is known (the reference returns it as an int):
     THE REFERENCE'S integer -- the (Gaussian, tile) instances of the 3-sigma rects, rasterizer_impl.cu:280-284 -- on every
     path (round 4: the asynchronous path handed out the count of instances actually binned); binned() is that other count."""
-    __slots__ = ("a", "opts", "pending", "R", "keep", "views", "outs")
+    __slots__ = ("a", "opts", "pending", "R", "keep", "views", "outs", "sets")
 
-    def __init__(self, a, opts, pending, R, keep=None, views=None, outs=None):
+    def __init__(self, a, opts, pending, R, keep=None, views=None, outs=None, sets=None):
         self.a, self.opts, self.pending, self.R = a, opts, pending, R
         self.keep = keep    # the tensors whose addresses `a` holds (converted / padded copies would otherwise be freed)
         self.views = views  # (MgsView array, V, the camera tensors it points to) of a view batch, else None
         self.outs = outs    # weak references to (out_color, out_feature): a recovery re-renders into them if they still live
+        self.sets = sets    # (S, int32 array of the V views' sets) of a set batch, else None
 
     def num_rendered_nowait(self) -> int:
         """The reference's count if the device has reported it, else -1 (never blocks)."""
@@ -211,11 +217,14 @@ def _binned_now(slot_ptr):
     return int(words[i]) & 0xffffffff
 
 
-def _launch_forward(L, a, views, radii, out_color, out_feat, slot_ptr, stream):
-    """mgs_rasterize_forward / mgs_rasterize_forward_views -> (rc, the reference's num_rendered or -1)."""
+def _launch_forward(L, a, views, sets, radii, out_color, out_feat, slot_ptr, stream):
+    """mgs_rasterize_forward / _views / _sets -> (rc, the reference's num_rendered or -1)."""
     nr = ctypes.c_int32(0)
     feat_ptr = out_feat.data_ptr() if (out_feat is not None and a.include_feature) else None
-    if views is not None:
+    if sets is not None:
+        rc = L.mgs_rasterize_forward_sets(ctypes.byref(a), views[1], views[0], sets[0], sets[1], radii.data_ptr(),
+                                          out_color.data_ptr(), feat_ptr, ctypes.byref(nr), slot_ptr, stream)
+    elif views is not None:
         rc = L.mgs_rasterize_forward_views(ctypes.byref(a), views[1], views[0], radii.data_ptr(), out_color.data_ptr(),
                                            feat_ptr, ctypes.byref(nr), slot_ptr, stream)
     else:
@@ -265,7 +274,7 @@ def recover_forward(handle, radii, dev):
     a.bwd_accum, a.bwd_accum_bytes = None, 0  # the first run's preprocess zeroed the accumulators; nothing touched them since
     slot_ptr, tag = st.take_slot()
     a.status_tag = tag
-    rc, R2 = _launch_forward(L, a, handle.views, radii, out_color, out_feat, slot_ptr, _stream(dev))
+    rc, R2 = _launch_forward(L, a, handle.views, handle.sets, radii, out_color, out_feat, slot_ptr, _stream(dev))
     _lib.check(rc, "rasterizer forward (re-run after a workspace overflow)")
     newp = _state.Pending(a, V, slot_ptr, p.key)
     st.add(newp)  # (the marks learn the binned count from its report)
@@ -276,31 +285,34 @@ def recover_forward(handle, radii, dev):
     return R2
 
 
-def _grad_layout(L, P, M, F, V, precomp=False):
+def _grad_layout(L, P, M, F, V, precomp=False, S=0):
     """Float sizes of the backward's single allocation: [scratch | dL_dcolors | dL_dfeature | means3D | opacity | sh |
     scales | rotations | cov3D | means2D | pad].  The first three regions are the accumulators; the gradients of the
     Gaussian PARAMETERS (colours or SH, features, means, opacity, scales, rotations) are contiguous, so one all-reduce
     over the span they cover (parallel.flat_alias) moves nothing else.  A batch of V views has V x P means2D rows and,
-    unless its colours are precomputed (precomp: one per Gaussian), V x P colour rows."""
-    k = (P, M, F, V, precomp and V > 0)
+    unless its colours are precomputed (precomp: one per Gaussian), V x P colour rows.  A batch of S Gaussian sets (S > 0,
+    P per set) has S x P rows of every per-Gaussian gradient."""
+    k = (P, M, F, V, precomp and V > 0, S)
     v = _LAYOUTS.get(k)
     if v is None:
-        scratch = L.mgs_views_backward_scratch_bytes(P, M, F, V) if V else L.mgs_backward_scratch_bytes(P, M, F)
+        scratch = L.mgs_sets_backward_scratch_bytes(P, M, F, V, S) if S else \
+            L.mgs_views_backward_scratch_bytes(P, M, F, V) if V else L.mgs_backward_scratch_bytes(P, M, F)
         scratch_f = (scratch + 3) // 4
         n = max(V, 1) * P  # (view, Gaussian) pairs
-        ncol = P if precomp else n
-        sizes = [scratch_f, 3 * ncol, F * P, 3 * P, P, 3 * M * P, 3 * P, 4 * P, 6 * P, 3 * n, 4]
-        accum_bytes = ((scratch_f + 3 * ncol + F * P) * 4 + 15) // 16 * 16  # may reach into the next, fully rewritten, region
+        G = max(S, 1) * P  # (set, Gaussian) rows
+        ncol = G if precomp else n
+        sizes = [scratch_f, 3 * ncol, F * G, 3 * G, G, 3 * M * G, 3 * G, 4 * G, 6 * G, 3 * n, 4]
+        accum_bytes = ((scratch_f + 3 * ncol + F * G) * 4 + 15) // 16 * 16  # may reach into the next, fully rewritten, region
         v = _LAYOUTS[k] = (sizes, accum_bytes)
     return v
 
 
-def _grad_offsets(L, P, M, F, V, precomp=False):
+def _grad_offsets(L, P, M, F, V, precomp=False, S=0):
     """(float offsets of the regions of _grad_layout, total floats)."""
-    k = (P, M, F, V, precomp and V > 0, "offs")
+    k = (P, M, F, V, precomp and V > 0, S, "offs")
     v = _LAYOUTS.get(k)
     if v is None:
-        sizes, _ = _grad_layout(L, P, M, F, V, precomp)
+        sizes, _ = _grad_layout(L, P, M, F, V, precomp, S)
         offs, o = [], 0
         for n in sizes:
             offs.append(o)
@@ -347,13 +359,19 @@ def rasterize_gaussians(background, means3D, colors, language_feature, opacity, 
 
 def _forward(background, means3D, colors, language_feature, opacity, scales, rotations, scale_modifier, cov3D_precomp,
              viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered,
-             debug, include_feature, want_grad_buffer, blocking=False, views=None):
+             debug, include_feature, want_grad_buffer, blocking=False, views=None, sets=None):
     """rasterize_gaussians + (want_grad_buffer) the backward's allocation, whose accumulator block the forward's
     preprocess kernel zeroes on the side: returns (ForwardHandle or int, color, feature, radii, geom, binning, img,
     grad_buffer or None).  views = (MgsView array, V, the camera tensors it points to): V views of the one Gaussian set in
-    one call (manigaussian_amd/views.py; the camera arguments are unused): color [V,3,H,W], feature [V,F,H,W], radii [V,P]."""
+    one call (manigaussian_amd/views.py; the camera arguments are unused): color [V,3,H,W], feature [V,F,H,W], radii [V,P].
+    sets = (S, int32 array of V set indices) with views: the V views render S Gaussian sets of P each, every Gaussian input
+    stacked [S,P,.] (views.py GaussianRasterizerBatch with view_sets)."""
     L = _lib.lib()
-    if means3D.ndimension() != 2 or means3D.size(1) != 3:
+    S = sets[0] if sets is not None else 0
+    if S:
+        if means3D.ndimension() != 3 or means3D.size(0) != S or means3D.size(2) != 3:
+            raise RuntimeError(f"means3D of a set batch must have dimensions ({S}, num_points, 3)")
+    elif means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:59-61
     if not means3D.is_cuda:
         raise RuntimeError("diff_gaussian_rasterization (MI355X build) needs tensors on a HIP device; "
@@ -361,7 +379,7 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
     dev = means3D.device
     V = views[1] if views is not None else 0
     lead = (V,) if V else ()
-    P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
+    P, H, W = int(means3D.size(-2)), int(image_height), int(image_width)
     means3D = _f32c(means3D, "means3D", dev)
     background = _f32c(background, "background", dev)
     colors = _f32c(colors, "colors_precomp", dev)
@@ -373,14 +391,16 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
     projmatrix = _f32c(projmatrix, "projmatrix", dev)
     campos = _f32c(campos, "campos", dev)
     sh = _f32c(sh, "sh", dev)
-    M = int(sh.size(1)) if sh.numel() != 0 else 0
+    M = _sh_coeffs(sh, S)
     include_feature = bool(include_feature)
     F = F_user = 0
     if include_feature:
-        if language_feature.ndimension() != 2 or language_feature.size(0) != P:
+        if S and (language_feature.ndimension() != 3 or language_feature.shape[:2] != (S, P)):
+            raise RuntimeError(f"language_feature_precomp of a set batch must have dimensions ({S}, num_points, F)")
+        if not S and (language_feature.ndimension() != 2 or language_feature.size(0) != P):
             raise RuntimeError("language_feature_precomp must have dimensions (num_points, F)")
         language_feature = _f32c(language_feature, "language_feature_precomp", dev)
-        F_user = int(language_feature.size(1))
+        F_user = int(language_feature.size(-1))
         F = _padded_F(F_user)
         if F != F_user:  # feature widths that are not compiled in: zero channels change nothing
             language_feature = torch.nn.functional.pad(language_feature, (0, F - F_user))
@@ -402,7 +422,8 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
         tmpl, opts = _template(P, int(degree), M, F, W, H, float(tan_fovx), float(tan_fovy), float(scale_modifier),
                                bool(prefiltered), bool(debug), include_feature)
         # (the marks key of a batch is parsed by the compiled binding's marks store: csrc/mgs_torch.cpp Key)
-        key = ("views", V, P, W, H, F, opts["tight_bins"]) if V else (P, W, H, F, opts["tight_bins"])
+        key = ("sets", S, V, P, W, H, F, opts["tight_bins"]) if S else \
+            ("views", V, P, W, H, F, opts["tight_bins"]) if V else (P, W, H, F, opts["tight_bins"])
         T = max(V, 1) * ((W + 15) // 16) * ((H + 15) // 16)  # the tiles binned: those of every view
         cannot_overflow, cap_worst, pool_worst, worst_bytes = _worst_case(L, P, W, H, F, V, T, dev)
         # ... charged against what live forwards of this device already hold (a node keeps its workspace until its backward):
@@ -473,12 +494,12 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
             a.binning_capacity, a.chunk_pool, a.async_forward = cap, pool, int(lazy)
         grad_buffer = None
         if want_grad_buffer:
-            sizes, accum_bytes = _grad_layout(L, P, M, F, V, colors.numel() != 0)
+            sizes, accum_bytes = _grad_layout(L, P, M, F, V, colors.numel() != 0, S)
             grad_buffer = torch.empty((sum(sizes),), dtype=_F32, device=dev)
             a.bwd_accum, a.bwd_accum_bytes = grad_buffer.data_ptr(), accum_bytes
         stream = _stream(dev)
-        what = "rasterize views" if V else "rasterize_gaussians"
-        rc, R = _launch_forward(L, a, views, radii, out_color, out_feat, slot_ptr, stream)
+        what = "rasterize sets" if S else "rasterize views" if V else "rasterize_gaussians"
+        rc, R = _launch_forward(L, a, views, sets, radii, out_color, out_feat, slot_ptr, stream)
         pending = binning2 = None
         while rc == _lib.MGS_NEED_CAPACITY:  # (waiting path) first call for this shape, or the scene grew: bin + render again
             st.learn(key, _binned_now(slot_ptr))  # the marks hold BINNED counts (advisor r4: not the 3-sigma-rect count R)
@@ -490,12 +511,12 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
                 _lib.check(L.mgs_rasterize_forward_render(ctypes.byref(a), R, radii.data_ptr(), out_color.data_ptr(),
                                                           feat_ptr, stream), what)
                 break
-            # the ABI has no render-only entry for a batch: the whole batch runs again, with room for R
+            # the ABI has no render-only entry for a batch: the whole batch (of views or of sets) runs again, with room for R
             a.binning_capacity = cap
             _lib.fill_options(a, opts)
             _lib.auto_seg(a, opts, st.marks.get(key)[0], T)
             slot_ptr, a.status_tag = st.take_slot()
-            rc, R = _launch_forward(L, a, views, radii, out_color, out_feat, slot_ptr, stream)
+            rc, R = _launch_forward(L, a, views, sets, radii, out_color, out_feat, slot_ptr, stream)
         else:
             _lib.check(rc, what)
             # a forward that a backward will follow can be repaired there if it overflowed (recover_forward)
@@ -505,7 +526,8 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
             st.add(pending)  # captured forwards report at every replay: _state.check_status()
         handle = ForwardHandle(a, opts, pending, R, (background, means3D, sh, colors, language_feature, opacity, scales,
                                                      rotations, cov3D_precomp, viewmatrix, projmatrix, campos),
-                               views=views, outs=(_weak(out_color), _weak(out_feat) if include_feature and F == F_user else None))
+                               views=views, outs=(_weak(out_color), _weak(out_feat) if include_feature and F == F_user else None),
+                               sets=sets)
         if _SPLIT_WORKSPACES:
             geom, img, binning = ws[0], ws[1], (binning2 if binning2 is not None else ws[2])
         elif blocking:  # the reference-shaped triple: three tensors whose byte counts describe their carving
@@ -566,24 +588,28 @@ def _backward(background, means3D, radii, colors, language_feature, scales, rota
     """rasterize_gaussians_backward; grad_buffer = the allocation _forward() handed out (accumulators already
     zeroed by the forward's preprocess kernel) or None.  R: the forward's ForwardHandle (its MgsRasterArgs is reused;
     the count may still be unknown) or the count as an int (buffers sized by mgs_binning_bytes).  The handle of a view
-    batch's forward (handle.views) takes cotangents [V,3,H,W] / [V,F,H,W] and gives dL_dmeans2D [V,P,3]."""
+    batch's forward (handle.views) takes cotangents [V,3,H,W] / [V,F,H,W] and gives dL_dmeans2D [V,P,3]; that of a set batch
+    (handle.sets) gives every per-Gaussian gradient as [S,P,.]."""
     L = _lib.lib()
     dev = means3D.device
-    P = int(means3D.size(0))
+    P = int(means3D.size(-2))
     H, W = int(dL_dout_color.size(-2)), int(dL_dout_color.size(-1))
-    M = int(sh.size(1)) if sh.numel() != 0 else 0
+    handle = R if isinstance(R, ForwardHandle) else None
+    S = handle.sets[0] if handle is not None and handle.sets is not None else 0
+    M = _sh_coeffs(sh, S)
     include_feature = bool(include_feature)
     dL_dout_color = _f32c(dL_dout_color, "dL_dout_color", dev)
     F = F_user = 0
     if include_feature:
-        F_user = int(language_feature.size(1))
+        F_user = int(language_feature.size(-1))
         F = _padded_F(F_user)
         dL_dout_language_feature = _f32c(dL_dout_language_feature, "dL_dout_language_feature", dev)
         if F != F_user:
             g = dL_dout_language_feature
             dL_dout_language_feature = torch.cat([g, g.new_zeros(g.shape[:-3] + (F - F_user, H, W))], -3)
-    handle = R if isinstance(R, ForwardHandle) else None
     V = handle.views[1] if handle is not None and handle.views is not None else 0
+    sets = handle.sets if handle is not None else None
+    lead = (S,) if S else ()  # per-Gaussian gradients of a set batch: [S,P,.]
     keep = None
     with _on_device(dev):
         if P == 0:
@@ -595,7 +621,7 @@ def _backward(background, means3D, radii, colors, language_feature, scales, rota
         # them with a single fill; everything else is fully written by the kernels.  Regions are addressed by offset
         # (no split / view tensors on the way in; one as_strided per gradient on the way out).
         (o_scr, o_col, o_feat, o_m3, o_op, o_sh, o_sc, o_rot, o_cov, o_m2, _o_pad), total = \
-            _grad_offsets(L, P, M, F, V, colors.numel() != 0)
+            _grad_offsets(L, P, M, F, V, colors.numel() != 0, S)
         prezeroed = grad_buffer is not None and grad_buffer.numel() == total
         flat = grad_buffer if prezeroed else torch.empty((total,), dtype=_F32, device=dev)
         base = flat.data_ptr()
@@ -632,20 +658,28 @@ def _backward(background, means3D, radii, colors, language_feature, scales, rota
                 base + 4 * o_op, base + 4 * o_col, (base + 4 * o_feat) if include_feature else None,
                 base + 4 * o_m3, base + 4 * o_cov, (base + 4 * o_sh) if M else None, base + 4 * o_sc, base + 4 * o_rot,
                 base + 4 * o_scr, (o_col - o_scr) * 4, _stream(dev))
-        if V:
+        if S:
+            _lib.check(L.mgs_rasterize_backward_sets(ctypes.byref(a), V, handle.views[0], S, sets[1], *args),
+                       "rasterize sets (backward)")
+        elif V:
             _lib.check(L.mgs_rasterize_backward_views(ctypes.byref(a), V, handle.views[0], *args), "rasterize views (backward)")
         else:
             _lib.check(L.mgs_rasterize_backward(ctypes.byref(a), *args), "rasterize_gaussians_backward")
-        view = flat.as_strided
-        g_m2 = view((V, P, 3), (3 * P, 3, 1), o_m2) if V else view((P, 3), (3, 1), o_m2)
-        g_feat = view((P, F), (F, 1), o_feat) if include_feature else torch.zeros((1,), dtype=_F32, device=dev)
-        g_sh = view((P, M, 3), (3 * M, 3, 1), o_sh) if M else flat.new_empty((P, 0, 3))
-        out = (g_m2, view((P, 3), (3, 1), o_col), g_feat, view((P, 1), (1, 1), o_op),
-               view((P, 3), (3, 1), o_m3), view((P, 6), (6, 1), o_cov), g_sh, view((P, 3), (3, 1), o_sc),
-               view((P, 4), (4, 1), o_rot))
+        def view(shape, off):  # a contiguous [lead, P, ...] region of the buffer
+            shape = lead + shape
+            strides, n = [], 1
+            for d in reversed(shape):
+                strides.append(n)
+                n *= d
+            return flat.as_strided(shape, tuple(reversed(strides)), off)
+        g_m2 = flat.as_strided((V, P, 3), (3 * P, 3, 1), o_m2) if V else view((P, 3), o_m2)
+        g_feat = view((P, F), o_feat) if include_feature else torch.zeros((1,), dtype=_F32, device=dev)
+        g_sh = view((P, M, 3), o_sh) if M else flat.new_empty(lead + (P, 0, 3))
+        out = (g_m2, view((P, 3), o_col), g_feat, view((P, 1), o_op), view((P, 3), o_m3), view((P, 6), o_cov), g_sh,
+               view((P, 3), o_sc), view((P, 4), o_rot))
     del keep
     if include_feature and F != F_user:
-        out = out[:2] + (out[2][:, :F_user].contiguous(),) + out[3:]
+        out = out[:2] + (out[2][..., :F_user].contiguous(),) + out[3:]
     return out
 
 

@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmgsplat.so")
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 c_fp = ctypes.c_void_p  # device pointers travel as integers (tensor.data_ptr())
 c_i32 = ctypes.c_int32
@@ -50,7 +50,7 @@ class MgsView(ctypes.Structure):
                 ("campos", c_fp)]
 
 
-MAX_VIEWS = 16
+MAX_VIEWS = 16  # views of a batch; also the most Gaussian sets of a set batch
 
 _EXPORTS = {
     # name: (restype, argtypes)
@@ -89,6 +89,11 @@ _EXPORTS = {
                                                    c_fp, c_fp, ctypes.POINTER(c_i32), c_fp, c_fp]),
     "mgs_rasterize_backward_views": (ctypes.c_int, [ctypes.POINTER(MgsRasterArgs), c_i32, ctypes.POINTER(MgsView), c_i32,
                                                     c_fp] + [c_fp] * 12 + [c_fp, c_sz, c_fp]),
+    "mgs_sets_backward_scratch_bytes": (c_sz, [ctypes.c_int] * 5),
+    "mgs_rasterize_forward_sets": (ctypes.c_int, [ctypes.POINTER(MgsRasterArgs), c_i32, ctypes.POINTER(MgsView), c_i32,
+                                                  ctypes.POINTER(c_i32), c_fp, c_fp, c_fp, ctypes.POINTER(c_i32), c_fp, c_fp]),
+    "mgs_rasterize_backward_sets": (ctypes.c_int, [ctypes.POINTER(MgsRasterArgs), c_i32, ctypes.POINTER(MgsView), c_i32,
+                                                   ctypes.POINTER(c_i32), c_i32, c_fp] + [c_fp] * 12 + [c_fp, c_sz, c_fp]),
     "mgs_mark_visible": (ctypes.c_int, [ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "mgs_deform_assemble_forward": (ctypes.c_int, [ctypes.c_int] * 4 + [c_fp] * 10 + [c_fp]),
     "mgs_deform_assemble_backward": (ctypes.c_int, [ctypes.c_int] * 5 + [c_fp] * 3 + [c_fp]),

@@ -197,27 +197,38 @@ static bool bucket_rank(const Options& o, int T) { return o.bin_mode == 2 && T <
 // atlas: V x the workgroups per launch, one set of launches per batch.  Per-Gaussian gradients are summed over the views on
 // the device (atomics for colour/feature rows, registers in the backward preprocess).  A single view is NOT a one-view atlas:
 // its image keeps H rows (workspace sizes and kernel arguments).  Past the entry points' own argument checks, everything takes a Pass.
+// A SET batch (mgs_rasterize_*_sets) is a view batch whose views render different Gaussian sets of one size, stacked [S][Pg][.]:
+// view v reads rows view_set[v] * Pg + i (ViewCam::row, RenderArgs::row), everything keyed by the virtual id is unchanged, and
+// the per-Gaussian gradients are [S][Pg][.], each set's summed over its own views.  A view batch is the set batch with S = 1.
 struct Pass {
   bool batch;             // the views entry points: cameras per view (use_cam), colours / cov3D per (view, Gaussian)
   int V, Pg, P;           // views, Gaussians per view, (virtual) Gaussians V * Pg
+  int S;                  // Gaussian sets (1 unless a set batch)
   int F;                  // feature channels rendered (0: none)
   int tiles_x, tiles_yv;  // tile grid of one view
   int T;                  // tiles of the image that is binned (all V views)
   int Hv, Hp, H;          // view height, rows per view in that image, its rows (what the img workspace is carved for)
   const MgsView* views;   // batch: the per-view cameras (nullptr in the size queries)
+  const int32_t* view_set;  // set batch: the set of every view (nullptr: every view renders set 0)
 };
 // V = 0: a single view; V >= 1: a batch of V views
-static Pass pass_of(int P, int W, int H, int F, int V, const MgsView* views = nullptr) {
+static Pass pass_of(int P, int W, int H, int F, int V, const MgsView* views = nullptr, int S = 1,
+                    const int32_t* view_set = nullptr) {
   Pass s;
   s.batch = V > 0; s.V = s.batch ? V : 1; s.Pg = P; s.P = P * s.V; s.F = F;
+  s.S = S > 0 ? S : 1;
   s.tiles_x = (W + TILE - 1) / TILE; s.tiles_yv = (H + TILE - 1) / TILE; s.T = s.tiles_x * s.tiles_yv * s.V;
   s.Hv = H; s.Hp = s.batch ? s.tiles_yv * TILE : H; s.H = s.batch ? s.V * s.Hp : H;
   s.views = views;
+  s.view_set = view_set;
   return s;
 }
-static Pass pass_of(const MgsRasterArgs* a, int V = 0, const MgsView* views = nullptr) {
-  return pass_of(a->P, a->W, a->H, a->include_feature ? a->F : 0, V, views);
+static Pass pass_of(const MgsRasterArgs* a, int V = 0, const MgsView* views = nullptr, int S = 1,
+                    const int32_t* view_set = nullptr) {
+  return pass_of(a->P, a->W, a->H, a->include_feature ? a->F : 0, V, views, S, view_set);
 }
+// first row of view v's Gaussian set in the stacked attribute tables
+static int set_row(const Pass& s, int v) { return s.view_set ? s.view_set[v] * s.Pg : 0; }
 static size_t geom_bytes(const Pass& s, int M) { size_t t; carve_geom(nullptr, s.P, M, s.T, s.V, &t); return t; }
 static size_t img_bytes(const Pass& s, int W) { size_t t; carve_img(nullptr, W, s.H, &t); return t; }
 
@@ -244,6 +255,12 @@ int mgs_views_chunk_pool_max(int R, int W, int H, int V) {
   return (int)chunk_pool_max(R > 0 ? (size_t)R : 1, views_shape(W, H, V).T);
 }
 size_t mgs_views_backward_scratch_bytes(int P, int M, int F, int V) { return mgs_backward_scratch_bytes(P * (V > 0 ? V : 1), M, F); }
+// (the scratch holds the render backward's sums per (view, Gaussian) pair; the per-set accumulators are the caller's
+//  dL_dcolors / dL_dfeature outputs)
+size_t mgs_sets_backward_scratch_bytes(int P, int M, int F, int V, int S) {
+  (void)S;
+  return mgs_views_backward_scratch_bytes(P, M, F, V);
+}
 
 static const uint64_t kStatusPending = ~0ull;
 
@@ -342,6 +359,7 @@ static void fill_camera(Args& p, const MgsRasterArgs* a, const Pass& s) {
     c.focal_y = a->H / (2.0f * w.tanfovy);
     c.focal_x = a->W / (2.0f * w.tanfovx);
     c.viewmatrix = w.viewmatrix; c.projmatrix = w.projmatrix; c.campos = w.campos;
+    c.row = set_row(s, v);
   }
 }
 
@@ -466,6 +484,7 @@ static RenderArgs render_args(const MgsRasterArgs* a, const Pass& s, const Optio
   r.nwf = fwd_waves(s.F, s.T);
   r.V = s.V; r.Pg = s.Pg; r.Hv = s.Hv; r.Hp = s.Hp;
   r.colors_per_view = s.batch && !a->colors_precomp;
+  for (int v = 0; v < MAX_VIEWS; v++) r.row[v] = v < s.V ? set_row(s, v) : 0;
   r.bg = a->background;
   r.colors = a->colors_precomp ? a->colors_precomp : g.rgb;
   r.feats = a->language_feature;
@@ -603,8 +622,8 @@ static int backward(const MgsRasterArgs* a, const Pass& s, int32_t R, const int3
   const BwdScratch sc = carve_bwd(scratch, s.P, a->M, F, nullptr);
   // accumulators the render backward adds into.  dL_dcolors is the gradient w.r.t. the per-Gaussian RGB whether it came from
   // colors_precomp or from SH (the reference returns it in both cases, rasterize_points.cu:169,224); a batch's has a row per
-  // (view, Gaussian) with SH colours (they differ per view)
-  const size_t P = (size_t)a->P, PV = (size_t)s.P, ncol = s.batch && !a->colors_precomp ? PV : P;
+  // (view, Gaussian) with SH colours (they differ per view); with colors_precomp, and for dL_dfeature, one per (set, Gaussian)
+  const size_t P = (size_t)a->P * s.S, PV = (size_t)s.P, ncol = s.batch && !a->colors_precomp ? PV : P;
   float* dcol = dL_dcolors;
   if (!a->accum_prezeroed)
   { StageTimer t(ST_BWD_MEMSET, stream);
@@ -628,7 +647,7 @@ static int backward(const MgsRasterArgs* a, const Pass& s, int32_t R, const int3
               "render backward", a->debug, stream);
   }
   BwdPreArgs p;
-  p.V = s.V; p.cov3D_per_view = s.batch && !a->cov3D_precomp;
+  p.V = s.V; p.S = s.S; p.cov3D_per_view = s.batch && !a->cov3D_precomp;
   p.P = a->P; p.D = a->D; p.M = a->M; p.W = a->W; p.H = a->H;
   fill_camera(p, a, s);
   p.scale_modifier = a->scale_modifier;
@@ -652,6 +671,26 @@ static int check_views(const MgsRasterArgs* a, int V, const MgsView* views) {
   for (int v = 0; v < V; v++)
     if (!views[v].viewmatrix || !views[v].projmatrix || !views[v].campos) { set_error("view %d: NULL matrix", v); return MGS_ERR_INVALID_ARG; }
   if (a->debug) { set_error("multi-view batches need debug 0"); return MGS_ERR_INVALID_ARG; }
+  return MGS_OK;
+}
+// A set batch: the view checks, 1 <= S <= MAX_VIEWS, every view's set in [0, S), and rows that fit the kernels' 32-bit indices.
+static int check_sets(const MgsRasterArgs* a, int V, const MgsView* views, int S, const int32_t* view_set) {
+  int rc = check_views(a, V, views);
+  if (rc) return rc;
+  if (S < 1 || S > MAX_VIEWS) { set_error("sets: need 1 <= S <= %d, got S = %d", MAX_VIEWS, S); return MGS_ERR_INVALID_ARG; }
+  if (!view_set) { set_error("sets: view_set is NULL"); return MGS_ERR_INVALID_ARG; }
+  for (int v = 0; v < V; v++)
+    if (view_set[v] < 0 || view_set[v] >= S) {
+      set_error("sets: view %d renders set %d, outside [0, %d)", v, view_set[v], S);
+      return MGS_ERR_INVALID_ARG;
+    }
+  const unsigned long long rows = (unsigned long long)a->P * (unsigned long long)S;
+  if (rows > 0x7fffffffull) { set_error("sets: S * P = %llu rows exceed 2^31 - 1", rows); return MGS_ERR_INVALID_ARG; }
+  if (a->include_feature && rows * (unsigned long long)a->F * 4ull >= (1ull << 32)) {
+    set_error("sets: S * P * F * 4 = %llu bytes of features: rows are addressed by 32-bit offsets (< 4 GiB)",
+              rows * (unsigned long long)a->F * 4ull);
+    return MGS_ERR_INVALID_ARG;
+  }
   return MGS_OK;
 }
 
@@ -703,18 +742,34 @@ int mgs_rasterize_forward(const MgsRasterArgs* a, int32_t* radii, float* out_col
   return forward(a, s, true, radii, out_color, out_feature, num_rendered, host_status, stream);
 }
 
-int mgs_rasterize_forward_views(const MgsRasterArgs* a, int32_t V, const MgsView* views, int32_t* radii, float* out_color,
-                                float* out_feature, int32_t* num_rendered, uint64_t* host_status, mgs_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  int rc = check_views(a, V, views);
-  if (rc) return rc;
+// The forward of a view batch (view_set == nullptr: one set) or of a set batch; the arguments are checked.
+static int forward_batch(const MgsRasterArgs* a, int V, const MgsView* views, int S, const int32_t* view_set, int32_t* radii,
+                         float* out_color, float* out_feature, int32_t* num_rendered, uint64_t* host_status,
+                         hipStream_t stream) {
   if (!num_rendered || !host_status) { set_error("num_rendered / host_status is NULL"); return MGS_ERR_INVALID_ARG; }
   *num_rendered = 0;
-  const Pass s = pass_of(a, V, views);
+  const Pass s = pass_of(a, V, views, S, view_set);
   bool done;
-  rc = check_outputs(a, s, out_color, out_feature, host_status, stream, &done);
+  const int rc = check_outputs(a, s, out_color, out_feature, host_status, stream, &done);
   if (rc || done) return rc;
   return forward(a, s, true, radii, out_color, out_feature, num_rendered, host_status, stream);
+}
+
+int mgs_rasterize_forward_views(const MgsRasterArgs* a, int32_t V, const MgsView* views, int32_t* radii, float* out_color,
+                                float* out_feature, int32_t* num_rendered, uint64_t* host_status, mgs_stream_t stream_) {
+  const int rc = check_views(a, V, views);
+  if (rc) return rc;
+  return forward_batch(a, V, views, 1, nullptr, radii, out_color, out_feature, num_rendered, host_status,
+                       (hipStream_t)stream_);
+}
+
+int mgs_rasterize_forward_sets(const MgsRasterArgs* a, int32_t V, const MgsView* views, int32_t S, const int32_t* view_set,
+                               int32_t* radii, float* out_color, float* out_feature, int32_t* num_rendered,
+                               uint64_t* host_status, mgs_stream_t stream_) {
+  const int rc = check_sets(a, V, views, S, view_set);
+  if (rc) return rc;
+  return forward_batch(a, V, views, S, view_set, radii, out_color, out_feature, num_rendered, host_status,
+                       (hipStream_t)stream_);
 }
 
 static int forward_result(const MgsRasterArgs* a, const Pass& s, const uint64_t* host_status, int32_t* num_rendered,
@@ -781,6 +836,19 @@ int mgs_rasterize_backward_views(const MgsRasterArgs* a, int32_t V, const MgsVie
   return backward(a, pass_of(a, V, views), R, radii, dL_dout_color, dL_dout_feature, dL_dmeans2D, dL_dconic, dL_dopacity,
                   dL_dcolors, dL_dfeature, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, scratch, scratch_bytes,
                   (hipStream_t)stream_);
+}
+
+int mgs_rasterize_backward_sets(const MgsRasterArgs* a, int32_t V, const MgsView* views, int32_t S, const int32_t* view_set,
+                                int32_t R, const int32_t* radii, const float* dL_dout_color, const float* dL_dout_feature,
+                                float* dL_dmeans2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolors, float* dL_dfeature,
+                                float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
+                                void* scratch, size_t scratch_bytes, mgs_stream_t stream_) {
+  int rc = check_sets(a, V, views, S, view_set);
+  if (rc) return rc;
+  if (a->P == 0) return MGS_OK;
+  return backward(a, pass_of(a, V, views, S, view_set), R, radii, dL_dout_color, dL_dout_feature, dL_dmeans2D, dL_dconic,
+                  dL_dopacity, dL_dcolors, dL_dfeature, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, scratch,
+                  scratch_bytes, (hipStream_t)stream_);
 }
 
 int mgs_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,

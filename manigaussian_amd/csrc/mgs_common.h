@@ -238,6 +238,7 @@ void set_error(const char* fmt, ...);
 constexpr int MAX_VIEWS = 16;
 struct ViewCam {  // per-view camera of a multi-view batch
   float tanfovx, tanfovy, focal_x, focal_y;
+  int row;  // first row of the view's Gaussian set in the stacked attribute tables: set x Pg (0 for a batch of one set)
   const float *viewmatrix, *projmatrix, *campos;
 };
 
@@ -296,11 +297,12 @@ struct RenderArgs {
   // that binning and compositing see one image of H = V * Hp rows (V == 1: H is the image height, Hv == H).
   // Instance ids are then "virtual": id = view * Pg + Gaussian.
   int V, Pg, Hv, Hp;
-  int colors_per_view;  // 1: `colors` is indexed by the virtual id (SH colours, per view), 0: by the Gaussian
+  int colors_per_view;  // 1: `colors` is indexed by the virtual id (SH colours, per view), 0: by the Gaussian's row
+  int row[MAX_VIEWS];   // view v's Gaussian i is row row[v] + i of feats and colors_precomp (ViewCam::row; 0 for one set)
   int dbg;  // MgsOptions.dbg without the preprocess's test hooks 512 / 1024 (the table at MgsOptions.dbg, include/mgsplat.h)
   const float* bg;
-  const float* colors;   // [P,3] colors_precomp or geom.rgb
-  const float* feats;    // [P,F]
+  const float* colors;   // geom.rgb [V*Pg,3] or colors_precomp [S*Pg,3]
+  const float* feats;    // [S*Pg,F]
   const float4* rec;     // geom.rec: [V*P][2] packed per-Gaussian record (the render kernels gather it by id)
 };
 
@@ -314,8 +316,10 @@ struct BwdPreArgs {
   int P, D, M, W, H;
   int cov3D_per_view;        // cov3D is the forward's [V][P][6] workspace copy (else the caller's [P][6])
   int use_cam;               // 1: cameras come from cam[] (the multi-view entry points)
-  int V;                     // views; P = Gaussians (not virtual); radii, clamped, acc8, dL_dcolor, dL_dmeans2D, dL_dconic
+  int V;                     // views; P = Gaussians per set (not virtual); radii, clamped, acc8, dL_dcolor, dL_dmeans2D, dL_dconic
   ViewCam cam[MAX_VIEWS];    // are [V][P][.] when V > 1 and cam[v] replaces the single-view camera fields below
+  int S;                     // Gaussian sets: inputs and per-Gaussian gradients are [S][P][.]; view v renders the set whose
+                             // rows start at cam[v].row (S == 1: every view renders set 0)
   float tanfovx, tanfovy, focal_x, focal_y, scale_modifier;
   const float *means3D, *shs, *scales, *rotations, *cov3D, *viewmatrix, *projmatrix, *campos;
   const int32_t* radii;

@@ -248,6 +248,9 @@ __global__ void __launch_bounds__(PRE_BLOCK) preprocess_fwd_kernel(FwdPreArgs a,
   const bool batch = a.use_cam != 0;
   const float tanfovx = batch ? a.cam[v].tanfovx : a.tanfovx, tanfovy = batch ? a.cam[v].tanfovy : a.tanfovy;
   const float focal_x = batch ? a.cam[v].focal_x : a.focal_x, focal_y = batch ? a.cam[v].focal_y : a.focal_y;
+  // the Gaussian's row in the attribute tables: its set's first row (wave-uniform) + gi.  Everything this kernel WRITES is
+  // keyed by the virtual id idx.
+  const size_t gr = (size_t)(batch ? a.cam[v].row : 0) + (size_t)gi;
   const int S = T;  // sort slices = tiles
   // direct binning (FwdPreArgs::direct_keys): two more tables behind the histogram -- this workgroup's reserved offset inside
   // every tile slice, and its write cursor there
@@ -272,7 +275,7 @@ __global__ void __launch_bounds__(PRE_BLOCK) preprocess_fwd_kernel(FwdPreArgs a,
   const float* __restrict__ vm = batch ? a.cam[v].viewmatrix : a.viewmatrix;
   const float* __restrict__ pm = batch ? a.cam[v].projmatrix : a.projmatrix;
   const float* __restrict__ campos = batch ? a.cam[v].campos : a.campos;
-  const V3 p = ld3(a.means3D, gi);
+  const V3 p = ld3(a.means3D, gr);
   const float view_z = row_view_z(vm[2], vm[6], vm[10], vm[14], p);
   if (view_z <= 0.2f) {  // auxiliary.h:154 near cull
     if (a.prefiltered) {
@@ -287,9 +290,9 @@ __global__ void __launch_bounds__(PRE_BLOCK) preprocess_fwd_kernel(FwdPreArgs a,
     float c6[6];
     if (a.cov3D_precomp) {
 #pragma unroll
-      for (int i = 0; i < 6; i++) c6[i] = a.cov3D_precomp[6 * (size_t)gi + i];
+      for (int i = 0; i < 6; i++) c6[i] = a.cov3D_precomp[6 * gr + i];
     } else {
-      cov3d_from_scale_rotation(a.rotations + 4 * (size_t)gi, ld3(a.scales, gi), a.scale_modifier, c6);
+      cov3d_from_scale_rotation(a.rotations + 4 * gr, ld3(a.scales, gr), a.scale_modifier, c6);
 #pragma unroll
       for (int i = 0; i < 6; i++) g.cov3D[6 * (size_t)idx + i] = c6[i];
     }
@@ -310,7 +313,7 @@ __global__ void __launch_bounds__(PRE_BLOCK) preprocess_fwd_kernel(FwdPreArgs a,
       get_rect(px, py, (int)my_radius, a.tiles_x, a.tiles_y, x0, y0, x1, y1);
       touched_ref = (uint32_t)((x1 - x0) * (y1 - y0));
       if ((x1 - x0) * (y1 - y0) != 0) {
-        const float opacity = a.opacities[gi];
+        const float opacity = a.opacities[gr];
         // bbox of {alpha >= 1/255} = {q(d) <= 2 ln(255 o)}: half extents sqrt(tau * cov_xx), sqrt(tau * cov_yy)
         // (cov = conic^-1 = the low-passed cov2D).  Inflated so it is conservative w.r.t. float rounding
         // of the per-pixel test; the per-pixel test itself stays exact.
@@ -328,7 +331,7 @@ __global__ void __launch_bounds__(PRE_BLOCK) preprocess_fwd_kernel(FwdPreArgs a,
           V3 dir = p - cam;
           const float len = sqrtf(dot(dir, dir));
           dir = {dir.x / len, dir.y / len, dir.z / len};
-          const float* __restrict__ sh = a.shs + (size_t)gi * a.M * 3;
+          const float* __restrict__ sh = a.shs + gr * a.M * 3;
           auto SH = [&](int k) { return v3(sh[3 * k], sh[3 * k + 1], sh[3 * k + 2]); };
           V3 res = SH_C0 * SH(0);
           if (a.D > 0) {
@@ -505,17 +508,25 @@ hipError_t launch_mark_visible(int P, const float* means3D, const float* view, c
 
 // ---- fused backward preprocess: K9 (conic -> cov3D, mean) + K10 (projection, SH, scale/rot) --------
 __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdPreArgs a) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  // one thread per (set, Gaussian); a workgroup never straddles sets (S == 1: one thread per Gaussian)
+  const int bps = (a.P + (int)blockDim.x - 1) / (int)blockDim.x;
+  const int set = (int)blockIdx.x / bps;
+  const int idx = ((int)blockIdx.x - set * bps) * (int)blockDim.x + (int)threadIdx.x;  // Gaussian of the set
   if (idx >= a.P) return;
+  const int row0 = set * a.P;  // the set's first row: views with cam[].row == row0 render it
   const size_t i = (size_t)idx;
+  const size_t gi = (size_t)row0 + i;  // row of the inputs and of every per-Gaussian gradient
   float g_mean[3] = {0, 0, 0}, g_cov[6] = {0, 0, 0, 0, 0, 0}, g_scale[3] = {0, 0, 0}, g_rot[4] = {0, 0, 0, 0};
   float g_op = 0.f;
   const int n_sh = a.M;
   bool sh_written = false;  // the first visible view stores the SH gradient, later views add to it
-  const V3 m = ld3(a.means3D, idx);
-  // One pass per view (a single-view call has V == 1): the render-backward sums, the clamp flags, the per-view colour
-  // gradient and the 2D outputs are [V][P][.]; everything per Gaussian is summed over the views in registers.
+  const V3 m = ld3(a.means3D, gi);
+  const bool batch = a.use_cam != 0;
+  // One pass per view of the set, in view order (a single-view call has V == 1): the render-backward sums, the clamp flags,
+  // the per-view colour gradient and the 2D outputs are [V][P][.]; everything per Gaussian is summed over the views in
+  // registers.
   for (int vw = 0; vw < a.V; vw++) {
+    if (batch && a.cam[vw].row != row0) continue;  // (workgroup-uniform) a view of another set
     const size_t vi = (size_t)vw * a.P + i;  // instance owner (virtual id)
     const bool vis = a.radii[vi] > 0;
     float acc[8];
@@ -534,7 +545,6 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdPreArgs a) {
       a.dL_dconic[4 * vi + 2] = 0.f;    a.dL_dconic[4 * vi + 3] = acc[4];
     }
     if (!vis) continue;
-    const bool batch = a.use_cam != 0;
     const float* __restrict__ vm = batch ? a.cam[vw].viewmatrix : a.viewmatrix;
     const float* __restrict__ proj = batch ? a.cam[vw].projmatrix : a.projmatrix;
     const float* __restrict__ campos = batch ? a.cam[vw].campos : a.campos;
@@ -543,7 +553,7 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdPreArgs a) {
     float gc[6] = {0, 0, 0, 0, 0, 0};  // this view's dL_dcov3D
     float c6[6];
 #pragma unroll
-    for (int k = 0; k < 6; k++) c6[k] = a.cov3D[6 * (a.cov3D_per_view ? vi : i) + k];
+    for (int k = 0; k < 6; k++) c6[k] = a.cov3D[6 * (a.cov3D_per_view ? vi : gi) + k];
     // ---- K9: backward.cu:144-274 ----
     const ViewCov vc = view_cov(m, vm, focal_x, focal_y, tanfovx, tanfovy);
     float c00, c01, c11, Va[3], Vb[3];
@@ -603,14 +613,14 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdPreArgs a) {
       const V3 dir_orig = m - cam;
       const float len = sqrtf(dot(dir_orig, dir_orig));
       const V3 dir = {dir_orig.x / len, dir_orig.y / len, dir_orig.z / len};
-      const float* __restrict__ sh = a.shs + i * n_sh * 3;
+      const float* __restrict__ sh = a.shs + gi * n_sh * 3;
       auto SH = [&](int k) { return v3(sh[3 * k], sh[3 * k + 1], sh[3 * k + 2]); };
       const uint8_t cl = a.clamped[vi];
       V3 dRGB = ld3(a.dL_dcolor, vi);
       dRGB.x *= (cl & 1) ? 0.f : 1.f;
       dRGB.y *= (cl & 2) ? 0.f : 1.f;
       dRGB.z *= (cl & 4) ? 0.f : 1.f;
-      float* __restrict__ o = a.dL_dsh + i * n_sh * 3;
+      float* __restrict__ o = a.dL_dsh + gi * n_sh * 3;
       auto ST = [&](int k, float w) {
         if (sh_written) { o[3 * k] += w * dRGB.x; o[3 * k + 1] += w * dRGB.y; o[3 * k + 2] += w * dRGB.z; }
         else { o[3 * k] = w * dRGB.x; o[3 * k + 1] = w * dRGB.y; o[3 * k + 2] = w * dRGB.z; }
@@ -662,15 +672,15 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdPreArgs a) {
     }
   }  // views
   if (a.dL_dsh && !sh_written)
-    for (int k = 0; k < 3 * n_sh; k++) a.dL_dsh[i * 3 * n_sh + k] = 0.f;
-  a.dL_dopacity[i] = g_op;
+    for (int k = 0; k < 3 * n_sh; k++) a.dL_dsh[gi * 3 * n_sh + k] = 0.f;
+  a.dL_dopacity[gi] = g_op;
   {
     // ---- cov3D backward, backward.cu:278-341 (linear in dL_dcov3D: applied once to the sum over the views) ----
     if (a.scales) {
       float R[3][3];
-      const float* q = a.rotations + 4 * i;
+      const float* q = a.rotations + 4 * gi;
       quat_rows(q, R);
-      const V3 s0 = ld3(a.scales, idx);
+      const V3 s0 = ld3(a.scales, gi);
       const float sc[3] = {a.scale_modifier * s0.x, a.scale_modifier * s0.y, a.scale_modifier * s0.z};
       const float dS[3][3] = {{g_cov[0], 0.5f * g_cov[1], 0.5f * g_cov[2]},
                               {0.5f * g_cov[1], g_cov[3], 0.5f * g_cov[4]},
@@ -696,16 +706,16 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdPreArgs a) {
     }
   }
 #pragma unroll
-  for (int k = 0; k < 3; k++) a.dL_dmeans3D[3 * i + k] = g_mean[k];
+  for (int k = 0; k < 3; k++) a.dL_dmeans3D[3 * gi + k] = g_mean[k];
 #pragma unroll
-  for (int k = 0; k < 6; k++) a.dL_dcov3D[6 * i + k] = g_cov[k];
+  for (int k = 0; k < 6; k++) a.dL_dcov3D[6 * gi + k] = g_cov[k];
   if (a.dL_dscales) {
 #pragma unroll
-    for (int k = 0; k < 3; k++) a.dL_dscales[3 * i + k] = g_scale[k];
+    for (int k = 0; k < 3; k++) a.dL_dscales[3 * gi + k] = g_scale[k];
   }
   if (a.dL_drot) {
 #pragma unroll
-    for (int k = 0; k < 4; k++) a.dL_drot[4 * i + k] = g_rot[k];
+    for (int k = 0; k < 4; k++) a.dL_drot[4 * gi + k] = g_rot[k];
   }
 }
 
@@ -714,7 +724,8 @@ hipError_t launch_preprocess_bwd(const BwdPreArgs& a, hipStream_t s) {
   // one wave per workgroup for small sets: 256 single-wave workgroups reach every CU at ManiGaussian's 16 384 Gaussians
   // (8.4 -> 7.8 us by the stage timers; no difference from 100 000 Gaussians up)
   const int bb = a.P <= 32768 ? 64 : 256;
-  hipLaunchKernelGGL(preprocess_bwd_kernel, dim3((a.P + bb - 1) / bb), dim3(bb), 0, s, a);
+  const int sets = a.S > 0 ? a.S : 1;  // (S x the workgroups: a workgroup never straddles sets)
+  hipLaunchKernelGGL(preprocess_bwd_kernel, dim3(sets * ((a.P + bb - 1) / bb)), dim3(bb), 0, s, a);
   return hipGetLastError();
 }
 

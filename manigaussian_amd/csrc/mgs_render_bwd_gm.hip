@@ -105,6 +105,7 @@ __global__ void __launch_bounds__(NW * 64, TWO ? 4 : 1) gm_bwd_kernel(RenderArgs
   const size_t pix = p.pixl;
   const uint32_t lc = last_chunk[((size_t)tile * 4 + sub) * 64 + lane];
   const uint2 rng = ranges[tile];
+  const uint32_t gbase = gauss_base(r, tile);        // instance id -> Gaussian row (block-uniform)
   const uint2 nsv = nsurv[(size_t)tile * 4 + sub];  // {survivors the forward listed for this block, round 0's first record}
   const uint32_t nsb = nsv.x;
   float dLc[3] = {0.f, 0.f, 0.f};
@@ -334,7 +335,7 @@ __global__ void __launch_bounds__(NW * 64, TWO ? 4 : 1) gm_bwd_kernel(RenderArgs
       const float op = has ? rec.g1.y : 0.f;
       const uint32_t pos = has ? rec.pos : 0xffffffffu;
       const uint32_t id = rec.id;                 // instance id (virtual in a multi-view batch): acc8 / per-view colour row
-      const uint32_t gidn = gauss_of(r, id);      // the Gaussian: feature row, feature gradient
+      const uint32_t gidn = gauss_of(gbase, id);  // the Gaussian: feature row, feature gradient
       const uint32_t cid = r.colors_per_view ? id : gidn;
 
       float a_mx = 0.f, a_my = 0.f, a_cx = 0.f, a_cy = 0.f, a_cz = 0.f, a_op = 0.f, a_r = 0.f, a_g = 0.f, a_b = 0.f;

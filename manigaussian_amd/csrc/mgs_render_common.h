@@ -148,10 +148,15 @@ __device__ __forceinline__ PixBlk pix_blk(const RenderArgs& r, int tile, int sub
   p.pixa = (size_t)p.py * r.W + p.px;
   return p;
 }
-// Gaussian of a (possibly virtual) instance id
-__device__ __forceinline__ uint32_t gauss_of(const RenderArgs& r, uint32_t id) {
-  return r.V > 1 ? id % (uint32_t)r.Pg : id;
+// Row offset of a block's instances in the stacked feats / colors_precomp tables: instance id = v * Pg + i of view v is
+// Gaussian row[v] + i.  A view covers whole tile rows of the atlas (Hp), so every instance in a tile's list belongs to the
+// tile's view: the offset is block-uniform (scalar), taken once from the tile, and the pair loops add it to the id.
+__device__ __forceinline__ uint32_t gauss_base(const RenderArgs& r, int tile) {
+  const int v = r.V > 1 ? (tile / r.tiles_x) / (r.Hp / TILE) : 0;
+  return (uint32_t)r.row[v] - (uint32_t)v * (uint32_t)r.Pg;
 }
+// Gaussian row of a (possibly virtual) instance id of the block whose gauss_base() is gbase
+__device__ __forceinline__ uint32_t gauss_of(uint32_t gbase, uint32_t id) { return id + gbase; }
 
 template <bool EXACT>
 __device__ __forceinline__ bool cull_ok(const float4& g0, const float4& g1, const PixBlk& p) {

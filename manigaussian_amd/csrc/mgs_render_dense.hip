@@ -257,8 +257,13 @@ coop_fwd_pairs_kernel(RenderArgs r, const uint2* __restrict__ ranges, const uint
         for (int i = 0; i < (NVF > 0 ? NVF : 1); i++) fv[i] = 0.f;
         const bool valid = (uint32_t)lane < nmy[q];
         float* rp = reinterpret_cast<float*>(&recP[ci][0]) + (((lane >> 2) * 2 + (lane & 1)) * 12 + ((lane >> 1) & 1));
+        // instance id -> Gaussian row (block-uniform), derived from the tile where it is used: held in an SGPR across the
+        // rounds it adds scalar spills to the wide kernels
+        int tile_ = tile;
+        asm volatile("" : "+s"(tile_));
+        const uint32_t gbase = gauss_base(r, tile_);
         auto colour_row = [&](uint32_t id) {
-          const uint32_t gid = gauss_of(r, id);
+          const uint32_t gid = gauss_of(gbase, id);
           const uint32_t cid = r.colors_per_view ? id : gid;  // colour row: per view when it comes from SH
           rq = make_float4(r.colors[(size_t)cid * 3], r.colors[(size_t)cid * 3 + 1], r.colors[(size_t)cid * 3 + 2],
                            __uint_as_float(gid));
@@ -277,7 +282,7 @@ coop_fwd_pairs_kernel(RenderArgs r, const uint2* __restrict__ ranges, const uint
             // waves of the pair write these same zeros, each before its own reads); their feature row is the chunk's first
             // Gaussian's -- a row the blend reads anyway, here with weight 0
             rp[0] = 0.f; rp[2] = 0.f; rp[4] = 0.f; rp[6] = 0.f; rp[8] = 0.f; rp[10] = 0.f;
-            rq.w = __uint_as_float(gauss_of(r, sid[ci * CHS]));
+            rq.w = __uint_as_float(gauss_of(gbase, sid[ci * CHS]));
           }
         } else {
           float4 g0 = make_float4(0, 0, 0, 0), g1 = make_float4(0, 0, -1.f, -1.f);
@@ -286,7 +291,7 @@ coop_fwd_pairs_kernel(RenderArgs r, const uint2* __restrict__ ranges, const uint
             g0 = r.rec[2 * (size_t)id]; g1 = r.rec[2 * (size_t)id + 1];
             colour_row(id);
           } else {
-            rq.w = __uint_as_float(gauss_of(r, my_surv[qhead + ci * CHS]));
+            rq.w = __uint_as_float(gauss_of(gbase, my_surv[qhead + ci * CHS]));
           }
           // (both waves of the pair write the same values to the chunk's buffer, each before its own reads; the other readers of
           //  this buffer -- the previous round's phase B -- are behind the list barrier)

@@ -68,15 +68,19 @@ struct Counters {
 Counters& counters() { static Counters c; return c; }
 
 // shape key of the workspace marks: V = 0 single view (this file and manigaussian_amd/_C.py), V >= 1 a batch of V views
-// (manigaussian_amd/_C.py _forward, key ("views", V, P, W, H, F, tight_bins))
+// (manigaussian_amd/_C.py _forward, key ("views", V, P, W, H, F, tight_bins)); S >= 1 a batch of V views of S Gaussian sets
+// (key ("sets", S, V, P, W, H, F, tight_bins): never the marks of a view batch of the same V and P)
 struct Key {
   int32_t V, P, W, H, F, tight;
-  bool operator==(const Key& o) const { return V == o.V && P == o.P && W == o.W && H == o.H && F == o.F && tight == o.tight; }
+  int32_t S = 0;
+  bool operator==(const Key& o) const {
+    return V == o.V && P == o.P && W == o.W && H == o.H && F == o.F && tight == o.tight && S == o.S;
+  }
 };
 struct KeyHash {
   size_t operator()(const Key& k) const {
     uint64_t h = 0x9e3779b97f4a7c15ull;
-    for (int32_t v : {k.V, k.P, k.W, k.H, k.F, k.tight}) h = (h ^ (uint64_t)(uint32_t)v) * 0x100000001b3ull + 0x632be59bd9b4e019ull;
+    for (int32_t v : {k.V, k.P, k.W, k.H, k.F, k.tight, k.S}) h = (h ^ (uint64_t)(uint32_t)v) * 0x100000001b3ull + 0x632be59bd9b4e019ull;
     return (size_t)h;
   }
 };
@@ -782,10 +786,15 @@ py::object rasterize(const at::Tensor& means3D, const at::Tensor& means2D, const
 Key key_of(const py::tuple& t) {
   if (t.size() == 5) return Key{0, t[0].cast<int>(), t[1].cast<int>(), t[2].cast<int>(), t[3].cast<int>(), t[4].cast<int>()};
   if (t.size() == 7) return Key{t[1].cast<int>(), t[2].cast<int>(), t[3].cast<int>(), t[4].cast<int>(), t[5].cast<int>(), t[6].cast<int>()};
-  throw py::key_error("a marks key is (P, W, H, F, tight_bins) or ('views', V, P, W, H, F, tight_bins)");
+  if (t.size() == 8 && t[0].cast<std::string>() == "sets")
+    return Key{t[2].cast<int>(), t[3].cast<int>(), t[4].cast<int>(), t[5].cast<int>(), t[6].cast<int>(), t[7].cast<int>(),
+               t[1].cast<int>()};
+  throw py::key_error("a marks key is (P, W, H, F, tight_bins), ('views', V, P, W, H, F, tight_bins) or "
+                      "('sets', S, V, P, W, H, F, tight_bins)");
 }
 py::tuple tuple_of(const Key& k) {
   if (k.V == 0) return py::make_tuple(k.P, k.W, k.H, k.F, k.tight);
+  if (k.S > 0) return py::make_tuple("sets", k.S, k.V, k.P, k.W, k.H, k.F, k.tight);
   return py::make_tuple("views", k.V, k.P, k.W, k.H, k.F, k.tight);
 }
 

@@ -350,6 +350,33 @@ int mgs_novel_calib_host(int V, const float* c2w, const float* K, int W, int H, 
                          float trans_y, float trans_z, float scale, float* world_view_transform,
                          float* full_proj_transform, float* camera_center, float* fov, float* tanfov);
 
+/* ---- rendering losses (MG/neural_rendering.py:299-329, :90-106 _embed_loss_fn, :22-27 PSNR_torch; MG/loss.py:12-23) ----
+ * For V views (1 .. 16) of W x H pixels: color [V,3,H,W] and feature [V,F,H,W] (F <= 64) are the rasterizer's planar outputs,
+ * contiguous; gt_rgb / gt_embed are constants addressed by ELEMENT strides {view, channel, row, column} (host arrays of 4),
+ * so channel-last and channel-first tensors are read where they lie.  Per view v:
+ *   mse[v]   = sum (color - gt_rgb)^2 / (3 N)                            N = W H
+ *   psnr[v]  = 20 log10(1 / sqrt(mse[v])), 100 where mse[v] == 0         (computed on the device)
+ *   embed[v] = MGS_EMBED_COSINE: 1 - mean_pixels cos(feature_p, gt_embed_p), the norms clamped to 1e-8 outside the graph
+ *              (F.cosine_similarity); MGS_EMBED_L2: sum (feature - gt_embed)^2 / (F N); MGS_EMBED_L2_NORM: the same against
+ *              (g - min g) / (max g - min g + 1e-12), min / max over the view's target; 0 when feature or gt_embed is NULL
+ *   loss     = 0 + sum_v (w[v][0] mse[v] + w[v][1] embed[v]), accumulated in this order
+ * weights [V,2]: weights_host (read during the call: the values are kernel arguments, frozen into a captured graph) or
+ * weights_dev (read by the kernels: a captured graph follows in-place updates); both NULL: all ones.
+ * Outputs: terms [V,3] = (mse, embed, psnr); *loss; g_color [V,3,H,W] / g_feature [V,F,H,W] = d loss / d color, d loss /
+ * d feature (either may be NULL: not wanted).  workspace: mgs_render_loss_workspace_bytes(V, W, H) bytes, 16-byte aligned.
+ * 2 launches (3 for MGS_EMBED_L2_NORM), no atomics, no host synchronisation: results are bit-identical from run to run.
+ * mgs_render_loss_backward: out = *g_up (a device scalar) x unit, both buffers in one launch (a NULL out is skipped). */
+#define MGS_EMBED_COSINE 0
+#define MGS_EMBED_L2 1
+#define MGS_EMBED_L2_NORM 2
+size_t mgs_render_loss_workspace_bytes(int V, int W, int H);
+int mgs_render_loss_forward(int V, int F, int W, int H, const float* color, const float* gt_rgb, const int64_t* rgb_strides,
+                            const float* feature, const float* gt_embed, const int64_t* embed_strides, int embed_fn,
+                            const float* weights_host, const float* weights_dev, float* g_color, float* g_feature,
+                            float* terms, float* loss, void* workspace, size_t workspace_bytes, mgs_stream_t stream);
+int mgs_render_loss_backward(int V, int F, int W, int H, const float* g_up, const float* unit_color, const float* unit_feature,
+                             float* out_color, float* out_feature, mgs_stream_t stream);
+
 /* Per-stage device timing (hipEvents on the caller's stream), enabled with
  * mgs_set_option("profile", 1) (render backward only) or 2 (every stage).  mgs_profile_read waits for the
  * recorded events, writes the summed milliseconds and launch counts per stage ([mgs_profile_num_stages()]),

@@ -111,6 +111,11 @@ _EXPORTS = {
                         [c_fp] * 5 + [c_fp, c_fp]),
     "mgs_novel_calib_host": (ctypes.c_int, [ctypes.c_int, c_fp, c_fp, ctypes.c_int, ctypes.c_int] + [ctypes.c_float] * 6 +
                              [c_fp] * 5),
+    "mgs_render_loss_workspace_bytes": (c_sz, [ctypes.c_int] * 3),
+    "mgs_render_loss_forward": (ctypes.c_int, [ctypes.c_int] * 4 + [c_fp, c_fp, ctypes.POINTER(ctypes.c_int64), c_fp, c_fp,
+                                               ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.POINTER(ctypes.c_float),
+                                               c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_sz, c_fp]),
+    "mgs_render_loss_backward": (ctypes.c_int, [ctypes.c_int] * 4 + [c_fp] * 5 + [c_fp]),
     "mgs_forward_stats": (ctypes.c_int, [ctypes.POINTER(MgsRasterArgs), c_i32, ctypes.POINTER(ctypes.c_int64),
                                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), c_fp]),
     "mgs_debug_geom_layout": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(c_sz)] * 4),

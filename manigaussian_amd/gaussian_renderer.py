@@ -73,14 +73,29 @@ def render_sets(items, bg_color):
     language features are given; their Gaussian counts must be equal.  Gradients reach each item's tensors as they would
     through its own render() call: a leaf shared by several items gets the sum, a detached tensor gets none.
     'viewspace_points' of item v is row v of the batch's [V,P,3] gradient holder."""
+    return _render_sets(items, bg_color)[0]
+
+
+def render_sets_stacked(items, bg_color):
+    """render_sets(items, bg_color) together with the batch tensors its dicts are slices of: returns (list, batch) with
+    batch = {"render": [V,3,H,W], "render_embed": [V,F,H,W] (the rasterizer's [1] placeholder without language features),
+    "viewspace_points": [V,P,3], "radii": [V,P]}.  A loss taken on the batch tensors (manigaussian_amd.losses) hands autograd
+    the whole batch gradient at once; taken on the per-view slices, autograd first rebuilds it with a zero-fill and an add
+    per slice."""
+    return _render_sets(items, bg_color)
+
+
+def _render_sets(items, bg_color):
     its = [dict(it) if isinstance(it, dict) else dict(zip(_ITEM, it)) for it in items]
     if not its:
-        return []
+        return [], None
     first = its[0]
     device = first["pts_xyz"].device
     sh = first["features_color"] is not None
     feat = first["features_language"] is not None
-    bg = torch.tensor(bg_color, dtype=torch.float32, device=device)
+    # (a float32 device tensor is taken as it is: building one from a list is a host-to-device copy, which a graph capture
+    #  of the step cannot hold)
+    bg = bg_color if isinstance(bg_color, torch.Tensor) else torch.tensor(bg_color, dtype=torch.float32, device=device)
     settings = [_settings(it["data"], it["idx"], bg, 1 if sh else 3, feat) for it in its]
     for v, (it, st) in enumerate(zip(its, settings)):
         if (st.image_height, st.image_width) != (settings[0].image_height, settings[0].image_width):
@@ -112,5 +127,6 @@ def render_sets(items, bg_color):
         means3D=means3D, means2D=screenspace_points, shs=stack("features_color") if sh else None,
         colors_precomp=None if sh else stack("pts_rgb"), language_feature_precomp=feats, opacities=stack("opacity"),
         scales=stack("scales"), rotations=stack("rotations"), cov3D_precomp=None)
-    return [{"render": image[v], "render_embed": feature_image[v] if feat else feature_image,
-             "viewspace_points": screenspace_points[v], "radii": radii[v]} for v in range(V)]
+    views = [{"render": image[v], "render_embed": feature_image[v] if feat else feature_image,
+              "viewspace_points": screenspace_points[v], "radii": radii[v]} for v in range(V)]
+    return views, {"render": image, "render_embed": feature_image, "viewspace_points": screenspace_points, "radii": radii}

@@ -377,6 +377,51 @@ int mgs_render_loss_forward(int V, int F, int W, int H, const float* color, cons
 int mgs_render_loss_backward(int V, int F, int W, int H, const float* g_up, const float* unit_color, const float* unit_feature,
                              float* out_color, float* out_feature, mgs_stream_t stream);
 
+/* ---- fused LAMB step over flat moment buffers (MG/helpers/optim/lamb.py:47-111; no bias correction, as there) ----
+ * For any number of parameter tensors, fp32, in TWO launches.  Per tensor, with the hyper-parameters of its group:
+ *   g' = grad_scale g;  m = m beta1 + g' (1 - beta1);  v = v beta2 + g' g' (1 - beta2)
+ *   u = m / (sqrt(v) + eps) [+ weight_decay p  if weight_decay != 0]
+ *   weight_norm = min(sqrt(sum p^2), 10);  adam_norm = sqrt(sum u^2)
+ *   trust_ratio = 1 if weight_norm == 0 or adam_norm == 0, else weight_norm / adam_norm      (decided on the device)
+ *   p = p - lr (adam ? 1 : trust_ratio) u;   stats[tensor] = {weight_norm, adam_norm, trust_ratio}
+ * A tensor is cut into chunks of mgs_lamb_chunk_elems() elements (the last one shorter); a chunk never straddles tensors.
+ * All tables live in DEVICE memory and are read by the kernels (the host passes pointers only):
+ *   tensors   [n_tensors]  MgsLambTensor: p; g (NULL: the tensor is skipped -- no state, no decay, p and its stats untouched);
+ *                          numel; state_off = its first element in exp_avg / exp_avg_sq (a multiple of 4, and the tensor's
+ *                          slot there is padded to a multiple of 4 elements); group; flags (MGS_LAMB_*_ALIGNED: that pointer is
+ *                          16-byte aligned -> 16-byte accesses, else element-wise; per tensor); chunk0 = its first chunk,
+ *                          n_chunks = ceil(numel / chunk elements) >= 1, tensors in chunk order
+ *   groups    [n_groups]   MgsLambGroup: 1 - beta is formed by the caller in double and rounded once (torch's scalar alpha);
+ *                          lr_dev != NULL: the learning rate is read from that device float at run time (a captured graph
+ *                          follows in-place updates), else lr
+ *   chunk_map [n_chunks][2] int32 {tensor, chunk inside the tensor}
+ * exp_avg, exp_avg_sq: the flat moment buffers (16-byte aligned).  stats: float [n_tensors][3].  zero_grad != 0: g is zeroed
+ * after it was read.  workspace: mgs_lamb_workspace_bytes(n_chunks) bytes (one pair of partial sums per chunk).
+ * The moments pass writes one partial pair per chunk; every workgroup of the apply pass adds its tensor's pairs in the same
+ * fixed order.  No atomics, no host read, no allocation: bit-identical from run to run, capturable into a HIP graph. */
+#define MGS_LAMB_P_ALIGNED 1
+#define MGS_LAMB_G_ALIGNED 2
+typedef struct MgsLambTensor {
+  float* p;
+  float* g;
+  int64_t numel;
+  int64_t state_off;
+  int32_t group;
+  int32_t flags;
+  int32_t chunk0;
+  int32_t n_chunks;
+} MgsLambTensor; /* 48 bytes */
+typedef struct MgsLambGroup {
+  float lr, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay;
+  int32_t adam;
+  const float* lr_dev;
+} MgsLambGroup; /* 40 bytes */
+int mgs_lamb_chunk_elems(void);
+size_t mgs_lamb_workspace_bytes(int64_t n_chunks);
+int mgs_lamb_step(int n_tensors, int n_groups, int64_t n_chunks, const MgsLambTensor* tensors, const MgsLambGroup* groups,
+                  const int32_t* chunk_map, float* exp_avg, float* exp_avg_sq, float* stats, float grad_scale, int zero_grad,
+                  void* workspace, size_t workspace_bytes, mgs_stream_t stream);
+
 /* Per-stage device timing (hipEvents on the caller's stream), enabled with
  * mgs_set_option("profile", 1) (render backward only) or 2 (every stage).  mgs_profile_read waits for the
  * recorded events, writes the summed milliseconds and launch counts per stage ([mgs_profile_num_stages()]),

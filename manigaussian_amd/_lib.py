@@ -116,6 +116,10 @@ _EXPORTS = {
                                                ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.POINTER(ctypes.c_float),
                                                c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_sz, c_fp]),
     "mgs_render_loss_backward": (ctypes.c_int, [ctypes.c_int] * 4 + [c_fp] * 5 + [c_fp]),
+    "mgs_lamb_chunk_elems": (ctypes.c_int, []),
+    "mgs_lamb_workspace_bytes": (c_sz, [ctypes.c_int64]),
+    "mgs_lamb_step": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
+                                     ctypes.c_float, ctypes.c_int, c_fp, c_sz, c_fp]),
     "mgs_forward_stats": (ctypes.c_int, [ctypes.POINTER(MgsRasterArgs), c_i32, ctypes.POINTER(ctypes.c_int64),
                                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), c_fp]),
     "mgs_debug_geom_layout": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(c_sz)] * 4),

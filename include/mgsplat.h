@@ -422,6 +422,36 @@ int mgs_lamb_step(int n_tensors, int n_groups, int64_t n_chunks, const MgsLambTe
                   const int32_t* chunk_map, float* exp_avg, float* exp_avg_sq, float* stats, float grad_scale, int zero_grad,
                   void* workspace, size_t workspace_bytes, mgs_stream_t stream);
 
+/* ---- the agent's voxel grid, forward only (MG/voxel/voxel_grid.py:168-229, VoxelGrid.coords_to_bounding_voxel_grid) ----
+ * Scatter-mean of B clouds of N points, [features | xyz] per point, into V^3 voxels; C = Fc + 7 channels per voxel:
+ *   [0, Fc + 3)  the mean of the voxel's points (0 where there is none)      Fc + 3 .. Fc + 5  x, y, z index / V
+ *   Fc + 6       occupancy, 0 or 1
+ * Per batch item b and axis, every step one fp32 operation and every division correctly rounded, as the reference computes it:
+ *   res = (max - min) / (float(V) + 1e-12f);  idx = floor((p - (min - res)) / (res + 1e-12f)) clamped to [0, V + 1]
+ * A point with index 0 or V + 1 on some axis lies in the shell the reference crops away and is dropped: points outside the
+ * bounds, NaN, +-inf, and a point exactly on the lower bound (fp32 rounding puts it at index 0 in the reference too).
+ * Every voxel's points are added in ASCENDING POINT INDEX from 0.0f and divided once by float(count): the order of the
+ * reference's CPU scatter_add_, so the grid equals the reference module's CPU result bit for bit and is the same from run to
+ * run (no float atomics; integer atomics order nothing that reaches the result).  Any multiplicity, all N in one voxel included.
+ *   coords [B,N,3], features [B,N,Fc] (NULL iff Fc == 0), bounds DEVICE [B,6] = (xmin, ymin, zmin, xmax, ymax, zmax) per item,
+ *   read by the kernels; grid [B,C,V,V,V] (channels_first != 0) or [B,V,V,V,C], 16-byte aligned, every float written once.
+ * _images: the same cloud read in place from n_images <= MGS_VOXELIZE_MAX_SOURCES pairs of contiguous images, coords[i]
+ * [B,3,H,W] and features[i] [B,Fc,H,W] (HOST arrays of device pointers, HW = H W): point i HW + row W + col of an item is that
+ * pixel of image i -- the order of flattening camera after camera, row-major -- and N = n_images HW.
+ * Limits (MGS_ERR_INVALID_ARG before any launch): 1 <= B <= 65536; 0 <= N <= 2^24 (a float count is exact up to there); V >= 1;
+ * B V^3 < 2^31 and B N < 2^31; 0 <= Fc <= MGS_VOXELIZE_MAX_FEATURES; non-NULL pointers; grid and workspace 16-byte aligned.
+ * MGS_ERR_WORKSPACE: fewer than mgs_voxelize_workspace_bytes(B, N, V) bytes (0 for sizes outside the limits; a function of
+ * B, N, V only).  The call zeroes what it needs of the workspace itself.  N = 0 writes the background grid.
+ * Four launches on `stream` (clear, link, mean, write), no host read, no allocation: capturable into a HIP graph. */
+#define MGS_VOXELIZE_MAX_FEATURES 64
+#define MGS_VOXELIZE_MAX_SOURCES 8
+size_t mgs_voxelize_workspace_bytes(int B, int64_t N, int V);
+int mgs_voxelize_forward(int B, int64_t N, int V, int Fc, int channels_first, const float* coords, const float* features,
+                         const float* bounds, float* grid, void* workspace, size_t workspace_bytes, mgs_stream_t stream);
+int mgs_voxelize_forward_images(int B, int n_images, int64_t HW, int V, int Fc, int channels_first, const float* const* coords,
+                                const float* const* features, const float* bounds, float* grid, void* workspace,
+                                size_t workspace_bytes, mgs_stream_t stream);
+
 /* Per-stage device timing (hipEvents on the caller's stream), enabled with
  * mgs_set_option("profile", 1) (render backward only) or 2 (every stage).  mgs_profile_read waits for the
  * recorded events, writes the summed milliseconds and launch counts per stage ([mgs_profile_num_stages()]),

@@ -120,6 +120,10 @@ _EXPORTS = {
     "mgs_lamb_workspace_bytes": (c_sz, [ctypes.c_int64]),
     "mgs_lamb_step": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
                                      ctypes.c_float, ctypes.c_int, c_fp, c_sz, c_fp]),
+    "mgs_voxelize_workspace_bytes": (c_sz, [ctypes.c_int, ctypes.c_int64, ctypes.c_int]),
+    "mgs_voxelize_forward": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 3 + [c_fp] * 5 + [c_sz, c_fp]),
+    "mgs_voxelize_forward_images": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 3 +
+                                    [ctypes.POINTER(c_fp)] * 2 + [c_fp] * 3 + [c_sz, c_fp]),
     "mgs_forward_stats": (ctypes.c_int, [ctypes.POINTER(MgsRasterArgs), c_i32, ctypes.POINTER(ctypes.c_int64),
                                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), c_fp]),
     "mgs_debug_geom_layout": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(c_sz)] * 4),

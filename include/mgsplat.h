@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 9
+#define MGS_ABI_VERSION 10
 
 /* error codes */
 #define MGS_OK 0
@@ -451,6 +451,43 @@ int mgs_voxelize_forward(int B, int64_t N, int V, int Fc, int channels_first, co
 int mgs_voxelize_forward_images(int B, int n_images, int64_t HW, int V, int Fc, int channels_first, const float* const* coords,
                                 const float* const* features, const float* bounds, float* grid, void* workspace,
                                 size_t workspace_bytes, mgs_stream_t stream);
+
+/* ---- the Perceiver's attention, fused, fp32 (MG/agents/manigaussian_bc/perceiver_lang_io.py:102-145, class Attention) ----
+ *   out[b, i, h D + .] = sum_j drop(softmax_j(q_i . k_j * D^-0.5, masked keys at -FLT_MAX))_ij v_j     D = 64 only
+ * q [B,Nq,H D]; k and v rows of H D floats each, read where they lie (the two halves of a to_kv output [B,Nk,2 H D]: row stride
+ * 2 H D, v = k + H D); head h is columns [h D, h D + D) of a row.  Strides are in ELEMENTS: *_stride_b between batch items,
+ * *_stride_n between rows; the last dimension is unit-stride.  mask: bytes [B,Nk] (row stride mask_stride_b), 0 = the key's
+ * score is -FLT_MAX (masked_fill_(~mask, -finfo.max): a row whose keys are all masked attends uniformly), or NULL.
+ * Dropout on the probabilities after normalisation: element (b H + h, i, j) is kept iff word (j & 3) of
+ *   Philox4x32-10(counter = (j >> 2, i, b H + h, offset & 0xffffffff), key = (seed & 0xffffffff, (seed >> 32) ^ (offset >> 32)))
+ * is >= floor(dropout_p * 2^32), and kept elements are scaled by 1 / (1 - dropout_p).  rng_state: DEVICE {seed, offset}, two
+ * 64-bit words read by the kernels (a captured graph follows in-place updates); may be NULL when dropout_p == 0.
+ * forward: writes out (strides out_stride_*) and lse [B,H,Nq] = row maximum + log of the row sum of the undropped row.
+ * backward: out, lse of the forward, d_out (strides dout_stride_*) -> dq [B,Nq,H D] (dq_stride_*) and dkv: dk in columns
+ * [0, H D), dv in [H D, 2 H D) of rows of dkv_stride_n >= 2 H D floats.  workspace: the workspace-size query below (D_i).
+ * dropout_mask: the keep decisions of forward and backward as bytes [B H, Nq, Nk] (a test and debug aid).
+ * MGS_ERR_INVALID_ARG before any launch: D != 64; B, H, Nq or Nk < 1; B H > 65535; dropout_p outside [0, 1); a pointer the
+ * kernels read or write 16 bytes at a time (q, k, v, out, d_out, dq, dkv, workspace) not 16-byte aligned; a row stride below
+ * the row or a stride that is no multiple of 4.  B H Nq Nk is no limit: nothing of that size exists.
+ * No atomics: bit-identical from run to run.  No host read, no allocation, no state: capturable into a HIP graph. */
+typedef struct MgsAttentionArgs {
+  int32_t B, H, Nq, Nk, D;
+  float dropout_p;
+  const float* q;
+  const float* k;
+  const float* v;
+  const uint8_t* mask;
+  const uint64_t* rng_state;
+  int64_t q_stride_b, q_stride_n, k_stride_b, k_stride_n, v_stride_b, v_stride_n;
+  int64_t out_stride_b, out_stride_n, dout_stride_b, dout_stride_n;
+  int64_t dq_stride_b, dq_stride_n, dkv_stride_b, dkv_stride_n;
+  int64_t mask_stride_b;
+} MgsAttentionArgs;
+size_t mgs_attention_workspace_bytes(int B, int H, int Nq, int Nk);
+int mgs_attention_forward(const MgsAttentionArgs* a, float* out, float* lse, mgs_stream_t stream);
+int mgs_attention_backward(const MgsAttentionArgs* a, const float* out, const float* lse, const float* d_out, float* dq,
+                           float* dkv, void* workspace, size_t workspace_bytes, mgs_stream_t stream);
+int mgs_attention_dropout_mask(const MgsAttentionArgs* a, uint8_t* keep, mgs_stream_t stream);
 
 /* Per-stage device timing (hipEvents on the caller's stream), enabled with
  * mgs_set_option("profile", 1) (render backward only) or 2 (every stage).  mgs_profile_read waits for the

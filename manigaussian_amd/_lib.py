@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmgsplat.so")
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 c_fp = ctypes.c_void_p  # device pointers travel as integers (tensor.data_ptr())
 c_i32 = ctypes.c_int32
@@ -48,6 +48,14 @@ class MgsRasterArgs(ctypes.Structure):
 class MgsView(ctypes.Structure):
     _fields_ = [("tanfovx", ctypes.c_float), ("tanfovy", ctypes.c_float), ("viewmatrix", c_fp), ("projmatrix", c_fp),
                 ("campos", c_fp)]
+
+
+class MgsAttentionArgs(ctypes.Structure):
+    _fields_ = [("B", c_i32), ("H", c_i32), ("Nq", c_i32), ("Nk", c_i32), ("D", c_i32), ("dropout_p", ctypes.c_float),
+                ("q", c_fp), ("k", c_fp), ("v", c_fp), ("mask", c_fp), ("rng_state", c_fp)] + \
+               [(n, ctypes.c_int64) for n in ("q_stride_b", "q_stride_n", "k_stride_b", "k_stride_n", "v_stride_b", "v_stride_n",
+                                              "out_stride_b", "out_stride_n", "dout_stride_b", "dout_stride_n", "dq_stride_b",
+                                              "dq_stride_n", "dkv_stride_b", "dkv_stride_n", "mask_stride_b")]
 
 
 MAX_VIEWS = 16  # views of a batch; also the most Gaussian sets of a set batch
@@ -124,6 +132,10 @@ _EXPORTS = {
     "mgs_voxelize_forward": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 3 + [c_fp] * 5 + [c_sz, c_fp]),
     "mgs_voxelize_forward_images": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 3 +
                                     [ctypes.POINTER(c_fp)] * 2 + [c_fp] * 3 + [c_sz, c_fp]),
+    "mgs_attention_workspace_bytes": (c_sz, [ctypes.c_int] * 4),
+    "mgs_attention_forward": (ctypes.c_int, [ctypes.POINTER(MgsAttentionArgs), c_fp, c_fp, c_fp]),
+    "mgs_attention_backward": (ctypes.c_int, [ctypes.POINTER(MgsAttentionArgs)] + [c_fp] * 6 + [c_sz, c_fp]),
+    "mgs_attention_dropout_mask": (ctypes.c_int, [ctypes.POINTER(MgsAttentionArgs), c_fp, c_fp]),
     "mgs_forward_stats": (ctypes.c_int, [ctypes.POINTER(MgsRasterArgs), c_i32, ctypes.POINTER(ctypes.c_int64),
                                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), c_fp]),
     "mgs_debug_geom_layout": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(c_sz)] * 4),

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 10
+#define MGS_ABI_VERSION 11
 
 /* error codes */
 #define MGS_OK 0
@@ -265,7 +265,9 @@ int mgs_rasterize_backward_views(const MgsRasterArgs* a, int32_t V, const MgsVie
  * dL_dconic and, with SH colours, dL_dcolors are per view as in a view batch; every other gradient is [S,P,.]: row (s, i) sums
  * the views of set s, rows of a set no view renders are zero.  Each view's image and radii are those of a single-view call on
  * its set, bit for bit.  Workspaces are a V-view batch's (mgs_views_*_bytes, mgs_binning_direct_extra(P, V, ..));
- * mgs_forward_result_views reads the status words.  The accumulator block (bwd_accum) is acc8 | dL_dcolors | dL_dfeature
+ * mgs_forward_result_views reads the status words.  The accumulator block (bwd_accum) is acc16 | dL_dcolors | dL_dfeature
+ * (ABI v11: the scratch holds one 64-byte row of 16 floats per (view, Gaussian) -- the six geometry sums and, with SH colours,
+ * the three colour sums, which the preprocess backward copies to dL_dcolors -- where v10 had rows of 8)
  * with S x P rows for dL_dfeature and, with colors_precomp, for dL_dcolors.  With S = 1 and every view on set 0 this is
  * mgs_rasterize_forward_views / mgs_rasterize_backward_views. */
 size_t mgs_sets_backward_scratch_bytes(int P, int M, int F, int V, int S);

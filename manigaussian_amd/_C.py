@@ -617,7 +617,7 @@ def _backward(background, means3D, radii, colors, language_feature, scales, rota
             return (z(0, 3), z(0, 3), z(0, F_user) if include_feature else z(1), z(0, 1), z(0, 3), z(0, 6),
                     z(0, M, 3), z(0, 3), z(0, 4))
         # ONE allocation for the scratch accumulators and every gradient: the three regions the render backward
-        # accumulates into (acc8 | dL_dcolors | dL_dfeature) come first and are contiguous, so the library zeroes
+        # accumulates into (acc16 | dL_dcolors | dL_dfeature) come first and are contiguous, so the library zeroes
         # them with a single fill; everything else is fully written by the kernels.  Regions are addressed by offset
         # (no split / view tensors on the way in; one as_strided per gradient on the way out).
         (o_scr, o_col, o_feat, o_m3, o_op, o_sh, o_sc, o_rot, o_cov, o_m2, _o_pad), total = \

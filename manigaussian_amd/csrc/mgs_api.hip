@@ -624,26 +624,29 @@ static int backward(const MgsRasterArgs* a, const Pass& s, int32_t R, const int3
   // colors_precomp or from SH (the reference returns it in both cases, rasterize_points.cu:169,224); a batch's has a row per
   // (view, Gaussian) with SH colours (they differ per view); with colors_precomp, and for dL_dfeature, one per (set, Gaussian)
   const size_t P = (size_t)a->P * s.S, PV = (size_t)s.P, ncol = s.batch && !a->colors_precomp ? PV : P;
+  // With SH colours the render backward sums the colour gradient in acc16's slots 6-8 (one row per (view, Gaussian), like
+  // dL_dcolors then) and the preprocess backward copies it out; with colors_precomp it adds into dL_dcolors directly.
   float* dcol = dL_dcolors;
+  const bool merged = a->colors_precomp == nullptr;
   if (!a->accum_prezeroed)
   { StageTimer t(ST_BWD_MEMSET, stream);
-    // one fill when the caller laid acc8 | dL_dcolors | dL_dfeature out back to back (manigaussian_amd/_C.py, views.py do)
-    char* z0 = reinterpret_cast<char*>(sc.acc8);
-    char* z_end = z0 + 8 * PV * sizeof(float);
+    // one fill when the caller laid acc16 | dL_dcolors | dL_dfeature out back to back (manigaussian_amd/_C.py, views.py do)
+    char* z0 = reinterpret_cast<char*>(sc.acc16);
+    char* z_end = z0 + 16 * PV * sizeof(float);
     const bool adj_col = reinterpret_cast<char*>(dcol) >= z_end && reinterpret_cast<char*>(dcol) <= z0 + scratch_total + 64;
     const bool adj_feat = F == 0 || reinterpret_cast<char*>(dL_dfeature) == reinterpret_cast<char*>(dcol) + 3 * ncol * sizeof(float);
     if (adj_col && adj_feat) {
       char* end = reinterpret_cast<char*>(dcol) + (3 * ncol + (size_t)F * P) * sizeof(float);
       MGS_HIP(launch_zero_bytes(z0, (size_t)(end - z0), stream), "memset accumulators");
     } else {
-      MGS_HIP(launch_zero_bytes(sc.acc8, 8 * PV * sizeof(float), stream), "memset acc8");
-      MGS_HIP(launch_zero_bytes(dcol, 3 * ncol * sizeof(float), stream), "memset dL_dcolors");
+      MGS_HIP(launch_zero_bytes(sc.acc16, 16 * PV * sizeof(float), stream), "memset acc16");
+      if (!merged) MGS_HIP(launch_zero_bytes(dcol, 3 * ncol * sizeof(float), stream), "memset dL_dcolors");
       if (F > 0) MGS_HIP(launch_zero_bytes(dL_dfeature, (size_t)F * P * sizeof(float), stream), "memset dL_dfeature");
     } }
   if (R != 0) {  // R < 0: count unknown to the host (asynchronous forward) -- empty ranges make the kernel a no-op
     const RenderArgs r = render_args(a, s, o, g);
     StageTimer t(ST_RENDER_BWD, stream);
-    MGS_STAGE(launch_render_bwd_gm(r, b, im, cv, dL_dout_color, dL_dout_feature, sc.acc8, dcol, dL_dfeature, stream),
+    MGS_STAGE(launch_render_bwd_gm(r, b, im, cv, dL_dout_color, dL_dout_feature, sc.acc16, merged ? nullptr : dcol, dL_dfeature, stream),
               "render backward", a->debug, stream);
   }
   BwdPreArgs p;
@@ -653,7 +656,7 @@ static int backward(const MgsRasterArgs* a, const Pass& s, int32_t R, const int3
   p.scale_modifier = a->scale_modifier;
   p.means3D = a->means3D; p.shs = a->shs; p.scales = a->scales; p.rotations = a->rotations;
   p.cov3D = a->cov3D_precomp ? a->cov3D_precomp : g.cov3D;
-  p.radii = radii; p.clamped = g.clamped; p.acc8 = sc.acc8; p.dL_dcolor = dcol;
+  p.radii = radii; p.clamped = g.clamped; p.acc16 = sc.acc16; p.dL_dcolor = dcol;
   p.dL_dmeans2D = dL_dmeans2D; p.dL_dconic = dL_dconic; p.dL_dopacity = dL_dopacity; p.dL_dmeans3D = dL_dmeans3D;
   p.dL_dcov3D = dL_dcov3D; p.dL_dsh = dL_dsh; p.dL_dscales = dL_dscales; p.dL_drot = dL_drotations;
   { StageTimer t(ST_PREPROCESS_BWD, stream);

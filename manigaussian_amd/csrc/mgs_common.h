@@ -205,13 +205,14 @@ inline BinView carve_binning(void* p, int R, int T, int F, uint32_t pool, ChunkV
 
 // Backward scratch: per-Gaussian accumulators the render backward adds into.
 struct BwdScratch {
-  float* acc8;      // [P][8]: dmean2D.x, dmean2D.y, dconic.x, dconic.y, dconic.w, dopacity, -, -
+  float* acc16;     // [P][16], one 64-byte row per (view, Gaussian): dmean2D.x, dmean2D.y, dconic.x, dconic.y, dconic.w, dopacity,
+                    // then dR, dG, dB with SH colours (with colors_precomp they go to the caller's dL_dcolors); 9-15 unused
 };
 inline BwdScratch carve_bwd(void* p, int P, int M, int F, size_t* total) {
   Carver c(p);
   BwdScratch s;
   size_t Pa = P > 0 ? (size_t)P : 1;
-  s.acc8 = c.take<float>(8 * Pa);
+  s.acc16 = c.take<float>(16 * Pa);
   (void)M; (void)F;
   if (total) *total = c.total();
   return s;
@@ -309,14 +310,14 @@ struct RenderArgs {
 hipError_t launch_render_fwd_dense(const RenderArgs& r, const BinView& b, const ImgView& im, const ChunkView& cv,
                                    float* out_color, float* out_feat, StatusSink status, hipStream_t s);
 hipError_t launch_render_bwd_gm(const RenderArgs& r, const BinView& b, const ImgView& im, const ChunkView& cv,
-                                const float* dL_dcolor_px, const float* dL_dfeat_px, float* acc8, float* dL_dcolors,
-                                float* dL_dfeat, hipStream_t s);
+                                const float* dL_dcolor_px, const float* dL_dfeat_px, float* acc16, float* dL_dcolors,
+                                float* dL_dfeat, hipStream_t s);  // dL_dcolors == nullptr: the colour sums go to acc16's slots 6-8
 
 struct BwdPreArgs {
   int P, D, M, W, H;
   int cov3D_per_view;        // cov3D is the forward's [V][P][6] workspace copy (else the caller's [P][6])
   int use_cam;               // 1: cameras come from cam[] (the multi-view entry points)
-  int V;                     // views; P = Gaussians per set (not virtual); radii, clamped, acc8, dL_dcolor, dL_dmeans2D, dL_dconic
+  int V;                     // views; P = Gaussians per set (not virtual); radii, clamped, acc16, dL_dcolor, dL_dmeans2D, dL_dconic
   ViewCam cam[MAX_VIEWS];    // are [V][P][.] when V > 1 and cam[v] replaces the single-view camera fields below
   int S;                     // Gaussian sets: inputs and per-Gaussian gradients are [S][P][.]; view v renders the set whose
                              // rows start at cam[v].row (S == 1: every view renders set 0)
@@ -324,8 +325,8 @@ struct BwdPreArgs {
   const float *means3D, *shs, *scales, *rotations, *cov3D, *viewmatrix, *projmatrix, *campos;
   const int32_t* radii;
   const uint8_t* clamped;
-  const float* acc8;
-  const float* dL_dcolor;  // [P,3] gradient w.r.t. the per-Gaussian RGB
+  const float* acc16;
+  float* dL_dcolor;  // with SH: [V][P][3] OUTPUT, the gradient w.r.t. the per-view RGB, copied out of acc16's slots 6-8
   float *dL_dmeans2D, *dL_dconic, *dL_dopacity, *dL_dmeans3D, *dL_dcov3D, *dL_dsh, *dL_dscales, *dL_drot;
 };
 hipError_t launch_preprocess_bwd(const BwdPreArgs& a, hipStream_t s);

@@ -529,11 +529,17 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdPreArgs a) {
     if (batch && a.cam[vw].row != row0) continue;  // (workgroup-uniform) a view of another set
     const size_t vi = (size_t)vw * a.P + i;  // instance owner (virtual id)
     const bool vis = a.radii[vi] > 0;
-    float acc[8];
+    float acc[6];
+    V3 dRGB = {0.f, 0.f, 0.f};
     {
-      const float4 u = reinterpret_cast<const float4*>(a.acc8)[2 * vi];
-      const float4 v = reinterpret_cast<const float4*>(a.acc8)[2 * vi + 1];
+      const float4 u = reinterpret_cast<const float4*>(a.acc16)[4 * vi];
+      const float4 v = reinterpret_cast<const float4*>(a.acc16)[4 * vi + 1];
       acc[0] = u.x; acc[1] = u.y; acc[2] = u.z; acc[3] = u.w; acc[4] = v.x; acc[5] = v.y;
+      if (a.shs) {  // SH colours: the render backward summed dR, dG, dB in slots 6-8 of the same row; hand them to the caller
+        const float4 t = reinterpret_cast<const float4*>(a.acc16)[4 * vi + 2];
+        dRGB = {v.z, v.w, t.x};
+        a.dL_dcolor[3 * vi + 0] = dRGB.x; a.dL_dcolor[3 * vi + 1] = dRGB.y; a.dL_dcolor[3 * vi + 2] = dRGB.z;
+      }
     }
     // render-backward sums: a non-visible Gaussian is in no tile list, so they are already zero.
     a.dL_dmeans2D[3 * vi + 0] = acc[0];
@@ -616,7 +622,6 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdPreArgs a) {
       const float* __restrict__ sh = a.shs + gi * n_sh * 3;
       auto SH = [&](int k) { return v3(sh[3 * k], sh[3 * k + 1], sh[3 * k + 2]); };
       const uint8_t cl = a.clamped[vi];
-      V3 dRGB = ld3(a.dL_dcolor, vi);
       dRGB.x *= (cl & 1) ? 0.f : 1.f;
       dRGB.y *= (cl & 2) ? 0.f : 1.f;
       dRGB.z *= (cl & 4) ? 0.f : 1.f;

@@ -59,7 +59,11 @@ struct GmRec { float4 g0, g1; uint32_t id, pos; };
 // 148 vector issue slots per double step against 2 x 87, 14 s_nop against 30.  It needs 167 registers, hence 12 waves per
 // workgroup (3 per SIMD: 168 registers each) instead of 16 x 128; a block's chunks 12 .. 15 (rare) go to waves 0 .. 3 in a second
 // pass.  configs[2]: 55.3 -> 50.4 us; gradients equal the one-pixel form's to 1e-6 of the tensor max (another summation order).
-template <int F, bool FAST, int NW, int NWF_, bool TWO, bool PAIR = false>
+// MERGED (SH colours: the colour gradient is indexed like the geometry sums, by the instance id): the nine scalar sums of a
+// Gaussian leave as ONE 64-byte-aligned row of acc16 [Pv][16] (slots 0-5 geometry, 6-8 dR dG dB, 9-15 unused) -- a float
+// atomic is a 64-byte request at the memory side whether 12 or 64 of its bytes are used.  !MERGED (colors_precomp: the colour
+// gradient is the caller's [P][3] table, indexed by the Gaussian's row): geometry to acc16's slots 0-5, colours to dL_dcolors.
+template <int F, bool FAST, int NW, int NWF_, bool TWO, bool PAIR, bool MERGED>
 __global__ void __launch_bounds__(NW * 64, TWO ? 4 : 1) gm_bwd_kernel(RenderArgs r, const uint2* __restrict__ ranges,
                                                           const uint32_t* __restrict__ round_base,
                                                           const uint32_t* __restrict__ last_chunk,
@@ -68,7 +72,7 @@ __global__ void __launch_bounds__(NW * 64, TWO ? 4 : 1) gm_bwd_kernel(RenderArgs
                                                           const float* __restrict__ partial, float* __restrict__ q,
                                                           const float* __restrict__ final_T,
                                                           const float* __restrict__ dL_dpix,
-                                                          const float* __restrict__ dL_dpix_F, float* __restrict__ acc8,
+                                                          const float* __restrict__ dL_dpix_F, float* __restrict__ acc16,
                                                           float* __restrict__ dL_dcolors, float* __restrict__ dL_dfeat,
                                                           const float* __restrict__ T_mid,
                                                           const uint32_t* __restrict__ surv, size_t surv_stride,
@@ -334,7 +338,7 @@ __global__ void __launch_bounds__(NW * 64, TWO ? 4 : 1) gm_bwd_kernel(RenderArgs
       const float ex = rec.g0.x, ey = rec.g0.y, cx = rec.g0.z, cy = rec.g0.w, cz = rec.g1.x;
       const float op = has ? rec.g1.y : 0.f;
       const uint32_t pos = has ? rec.pos : 0xffffffffu;
-      const uint32_t id = rec.id;                 // instance id (virtual in a multi-view batch): acc8 / per-view colour row
+      const uint32_t id = rec.id;                 // instance id (virtual in a multi-view batch): acc16 / per-view colour row
       const uint32_t gidn = gauss_of(gbase, id);  // the Gaussian: feature row, feature gradient
       const uint32_t cid = r.colors_per_view ? id : gidn;
 
@@ -503,8 +507,9 @@ __global__ void __launch_bounds__(NW * 64, TWO ? 4 : 1) gm_bwd_kernel(RenderArgs
 
       if (first_it) MGS_BTRACE(g == 0 ? 8 : 6);
       // ---- hand the group's sums to memory: transpose through LDS so that every atomic instruction covers whole
-      //      rows (32 consecutive feature channels of one Gaussian = one 128-B line; 8 Gaussians x 6 geometry sums;
-      //      16 Gaussians x 3 colour sums) instead of 64 different lines.  (Nothing to hand over if no pixel of the
+      //      rows (32 consecutive feature channels of one Gaussian = one 128-B line; 4 Gaussians x 9 scalar sums, one
+      //      64-B row each -- or, with colors_precomp, 8 Gaussians x 6 geometry sums and 16 Gaussians x 3 colour sums)
+      //      instead of 64 different lines.  (Nothing to hand over if no pixel of the
       //      block blended anything of this group.) ----
       if (((g == 0 ? lm0 : lm1) & umask) != 0ull) {
         float v[9] = {a_mx * ddelx_dx, a_my * ddely_dy, -0.5f * a_cx, -0.5f * a_cy, -0.5f * a_cz, a_op, a_r, a_g, a_b};
@@ -552,7 +557,22 @@ __global__ void __launch_bounds__(NW * 64, TWO ? 4 : 1) gm_bwd_kernel(RenderArgs
             }
           }
         }
-        {
+        if constexpr (MERGED) {
+          uint32_t gm[8];
+          float tm[8];
+          const int i16 = lane & 15;
+#pragma unroll
+          for (int k = 0; k < 8; k++) {  // all nine sums: 4 Gaussians x 16 slots (9 used) per instruction, one 64-B row each
+            const int gg = 4 * k + (lane >> 4);
+            gm[k] = gid[w][gg].x;
+            tm[k] = tr[gg * TROW + NCT * 32 + (i16 < 9 ? i16 : 0)];
+          }
+#pragma unroll
+          for (int k = 0; k < 8; k++) asm volatile("" : "+v"(gm[k]), "+v"(tm[k]));
+#pragma unroll
+          for (int k = 0; k < 8; k++)
+            if (gm[k] != 0xffffffffu && i16 < 9) unsafeAtomicAdd(acc16 + (size_t)gm[k] * 16 + i16, tm[k]);
+        } else {
           uint32_t gq[4];
           uint2 gc[2];
           float tq[4], tc[2];
@@ -575,7 +595,7 @@ __global__ void __launch_bounds__(NW * 64, TWO ? 4 : 1) gm_bwd_kernel(RenderArgs
           for (int k = 0; k < 2; k++) asm volatile("" : "+v"(gc[k].x), "+v"(gc[k].y), "+v"(tc[k]));
 #pragma unroll
           for (int k = 0; k < 4; k++)
-            if (gq[k] != 0xffffffffu && i8 < 6) unsafeAtomicAdd(acc8 + (size_t)gq[k] * 8 + i8, tq[k]);
+            if (gq[k] != 0xffffffffu && i8 < 6) unsafeAtomicAdd(acc16 + (size_t)gq[k] * 16 + i8, tq[k]);
 #pragma unroll
           for (int k = 0; k < 2; k++)
             if (gc[k].x != 0xffffffffu && i4 < 3)
@@ -592,14 +612,17 @@ __global__ void __launch_bounds__(NW * 64, TWO ? 4 : 1) gm_bwd_kernel(RenderArgs
 // ------------------------------------------- dispatch ------------------------------------------------
 template <int F>
 static hipError_t gm_F(const RenderArgs& r, const ImgView& im, const ChunkView& cv, const float* dc, const float* df,
-                       float* acc8, float* dcol, float* dfeat, hipStream_t s) {
+                       float* acc16, float* dcol, float* dfeat, hipStream_t s) {
   const int T = r.tiles_x * r.tiles_y;
   const int grid = ((T + 7) / 8) * 32;
-#define MGS_GM(FAST, NW, NWF, TWO, PAIR)                                                                              \
-  hipLaunchKernelGGL((gm_bwd_kernel<F, FAST, NW, NWF, TWO, PAIR>), dim3(grid), dim3(NW * 64), 0, s, r, im.ranges,      \
-                     cv.round_base, cv.last_chunk, cv.T_end, cv.last_pos, cv.partial, cv.q, im.final_T, dc, df, acc8, \
+  // dcol == nullptr: SH colours, the colour sums share the geometry sums' row (MERGED)
+#define MGS_GM(FAST, NW, NWF, TWO, PAIR, MERGED)                                                                       \
+  hipLaunchKernelGGL((gm_bwd_kernel<F, FAST, NW, NWF, TWO, PAIR, MERGED>), dim3(grid), dim3(NW * 64), 0, s, r, im.ranges, \
+                     cv.round_base, cv.last_chunk, cv.T_end, cv.last_pos, cv.partial, cv.q, im.final_T, dc, df, acc16, \
                      dcol, dfeat, cv.T_mid, cv.surv, cv.surv_stride, cv.nsurv)
-#define MGS_GMF(NW, NWF, TWO, PAIR) do { if (r.fast_exp) MGS_GM(true, NW, NWF, TWO, PAIR); else MGS_GM(false, NW, NWF, TWO, PAIR); } while (0)
+#define MGS_GMM(FAST, NW, NWF, TWO, PAIR) \
+  do { if (dcol) MGS_GM(FAST, NW, NWF, TWO, PAIR, false); else MGS_GM(FAST, NW, NWF, TWO, PAIR, true); } while (0)
+#define MGS_GMF(NW, NWF, TWO, PAIR) do { if (r.fast_exp) MGS_GMM(true, NW, NWF, TWO, PAIR); else MGS_GMM(false, NW, NWF, TWO, PAIR); } while (0)
   if constexpr (F > 32) {
     MGS_GMF(8, 8, false, false);                 // wide rows: 8 waves x 256 registers (the forward ran 8 waves as well)
   } else if (r.nwf == 8) {
@@ -612,17 +635,18 @@ static hipError_t gm_F(const RenderArgs& r, const ImgView& im, const ChunkView& 
     MGS_GMF(12, 16, false, true);                // default: 12 waves x 168 registers, two pixels per step
   }
 #undef MGS_GMF
+#undef MGS_GMM
 #undef MGS_GM
   return hipGetLastError();
 }
 
 hipError_t launch_render_bwd_gm(const RenderArgs& r, const BinView& b, const ImgView& im, const ChunkView& cv,
-                                const float* dL_dcolor_px, const float* dL_dfeat_px, float* acc8, float* dL_dcolors,
+                                const float* dL_dcolor_px, const float* dL_dfeat_px, float* acc16, float* dL_dcolors,
                                 float* dL_dfeat, hipStream_t s) {
   (void)b;
   const int F = r.include_feature ? r.F : 0;
   switch (F) {
-#define X(N) case N: return gm_F<N>(r, im, cv, dL_dcolor_px, dL_dfeat_px, acc8, dL_dcolors, dL_dfeat, s);
+#define X(N) case N: return gm_F<N>(r, im, cv, dL_dcolor_px, dL_dfeat_px, acc16, dL_dcolors, dL_dfeat, s);
     MGS_FOR_EACH_F(X)
 #undef X
     default: return hipErrorInvalidValue;

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 11
+#define MGS_ABI_VERSION 12
 
 /* error codes */
 #define MGS_OK 0
@@ -490,6 +490,38 @@ int mgs_attention_forward(const MgsAttentionArgs* a, float* out, float* lse, mgs
 int mgs_attention_backward(const MgsAttentionArgs* a, const float* out, const float* lse, const float* d_out, float* dq,
                            float* dkv, void* workspace, size_t workspace_bytes, mgs_stream_t stream);
 int mgs_attention_dropout_mask(const MgsAttentionArgs* a, uint8_t* keep, mgs_stream_t stream);
+
+/* ---- the Perceiver's aggregated features, fused, fp32 (MG/helpers/network_utils.py:927-963, class SpatialSoftmax3D, and the
+ * nn.AdaptiveMaxPool3d(1) next to it at MG/agents/manigaussian_bc/perceiver_lang_io.py:384,485,504) -- ABI v12 ----
+ * feature [rows, N], N = D H W, contiguous, 16-byte aligned; a row is one (batch, channel), rows = B C, row = b C + c.
+ *   p = softmax(row / temperature);   keypoints[b, 3 c + (0, 1, 2)] = (sum p pos_x, sum p pos_y, sum p pos_z);   maxpool[b, c] = max(row)
+ * The positions are the reference's tables, np.meshgrid(linspace(-1, 1, D), linspace(-1, 1, H), linspace(-1, 1, W)) in its default
+ * 'xy' order flattened: for the flat index i = (a D + b) W + c (a < H, b < D, c < W), pos_x = lin_D[b], pos_y = lin_H[a],
+ * pos_z = lin_W[c], lin_n = linspace(-1, 1, n) ([-1] for n = 1).  For D != H they do not follow the volume's axes; that is the
+ * reference's behaviour.  The kernels compute them from the index; no table of N entries is read.
+ * forward: ONE read of feature.  Each row is cut into slices (slices = 0: chosen from rows and N; 1..64: forced, a test aid) of
+ * whole 16-byte vectors; a row that starts off a 16-byte boundary (N % 4 != 0) has its first and last elements read as scalars.
+ * A launch of rows x slices workgroups writes one 32-byte record per slice to the workspace; a second, small launch folds each
+ * row's records IN SLICE ORDER and writes keypoints (row stride keypoints_stride_b >= 3 C floats), maxpool (row stride
+ * maxpool_stride_b >= C; may be NULL) and stats [rows, 6] = (max, sum exp((x - max) / temperature), E_x, E_y, E_z, argmax as the
+ * bits of a uint32): all the backward needs.  argmax is the LOWEST flat index holding the maximum, for every split.
+ * backward: one launch, one read of feature and one write of g_feature [rows, N] (16-byte aligned, every float written once):
+ *   g_feature_i = p_i / temperature * sum_axis g_keypoints_axis (pos_axis(i) - E_axis) + g_max [i == argmax]
+ * g_keypoints [B, 3 C] and g_max [B, C] by row stride; either may be NULL (no such upstream gradient).
+ * MGS_ERR_INVALID_ARG before any launch: rows, C, D, H or W < 1; rows no multiple of C; D H W > 2^31 - 1; rows > (2^31 - 1) / 64;
+ * temperature not positive and finite; slices outside [0, 64]; a NULL pointer other than the optional ones; feature, g_feature or
+ * the workspace not 16-byte aligned; a row stride below its row.  MGS_ERR_WORKSPACE: fewer than
+ * mgs_spatial_softmax_workspace_bytes(rows, N) bytes (64 records per row: independent of the split; 0 for sizes outside the limits).
+ * A row that holds a non-finite value yields unspecified values for that row only.  Element offsets are 64-bit.
+ * No atomics, no workgroup waits for another, nothing to zero: bit-identical from run to run.  No host read, no allocation, no
+ * state: capturable into a HIP graph. */
+size_t mgs_spatial_softmax_workspace_bytes(int64_t rows, int64_t N);
+int mgs_spatial_softmax_forward(int64_t rows, int C, int D, int H, int W, float temperature, const float* feature,
+                                float* keypoints, int64_t keypoints_stride_b, float* maxpool, int64_t maxpool_stride_b,
+                                float* stats, void* workspace, size_t workspace_bytes, int slices, mgs_stream_t stream);
+int mgs_spatial_softmax_backward(int64_t rows, int C, int D, int H, int W, float temperature, const float* feature,
+                                 const float* stats, const float* g_keypoints, int64_t g_keypoints_stride_b, const float* g_max,
+                                 int64_t g_max_stride_b, float* g_feature, int slices, mgs_stream_t stream);
 
 /* Per-stage device timing (hipEvents on the caller's stream), enabled with
  * mgs_set_option("profile", 1) (render backward only) or 2 (every stage).  mgs_profile_read waits for the

@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmgsplat.so")
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 c_fp = ctypes.c_void_p  # device pointers travel as integers (tensor.data_ptr())
 c_i32 = ctypes.c_int32
@@ -136,6 +136,11 @@ _EXPORTS = {
     "mgs_attention_forward": (ctypes.c_int, [ctypes.POINTER(MgsAttentionArgs), c_fp, c_fp, c_fp]),
     "mgs_attention_backward": (ctypes.c_int, [ctypes.POINTER(MgsAttentionArgs)] + [c_fp] * 6 + [c_sz, c_fp]),
     "mgs_attention_dropout_mask": (ctypes.c_int, [ctypes.POINTER(MgsAttentionArgs), c_fp, c_fp]),
+    "mgs_spatial_softmax_workspace_bytes": (c_sz, [ctypes.c_int64] * 2),
+    "mgs_spatial_softmax_forward": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int] * 4 + [ctypes.c_float, c_fp, c_fp, ctypes.c_int64,
+                                                   c_fp, ctypes.c_int64, c_fp, c_fp, c_sz, ctypes.c_int, c_fp]),
+    "mgs_spatial_softmax_backward": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int] * 4 + [ctypes.c_float, c_fp, c_fp, c_fp,
+                                                    ctypes.c_int64, c_fp, ctypes.c_int64, c_fp, ctypes.c_int, c_fp]),
     "mgs_forward_stats": (ctypes.c_int, [ctypes.POINTER(MgsRasterArgs), c_i32, ctypes.POINTER(ctypes.c_int64),
                                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), c_fp]),
     "mgs_debug_geom_layout": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(c_sz)] * 4),

@@ -39,9 +39,21 @@ def _workspace(dev, B, H, Nq, Nk):
     return ws
 
 
+def _copy(t):
+    """A freshly allocated row-major copy (`.contiguous()` would hand back a tensor whose size-1 dimensions carry odd strides)."""
+    return t.clone(memory_format=torch.contiguous_format)
+
+
 def _by_stride(t):
-    """The tensor itself when the kernels can read it in place (unit-stride last dimension), else a contiguous copy."""
-    return t if t.stride(-1) == 1 else t.contiguous()
+    """The tensor itself when the library reads it in place -- what attn_check_qkv and bad_stride of mgs_attention.hip accept:
+    unit-stride last dimension, 16-byte aligned base, row stride at least the row, row and batch strides multiples of 4 floats
+    (a batch stride of 0, an `expand` over the batch, is one) -- else a row-major copy.  The halves of a to_kv output, a
+    16-byte aligned column slice and every nn.Linear output are read in place; a column slice at an odd offset, a buffer of odd
+    width and a row-expanded gradient (what `out.sum(1)` sends back) are copied."""
+    sb, sn, s1 = t.stride()
+    if s1 == 1 and t.data_ptr() % 16 == 0 and sn >= t.size(2) and sn % 4 == 0 and sb >= 0 and sb % 4 == 0:
+        return t
+    return _copy(t)
 
 
 def _fill(a, q, k, v, heads, mask, dropout_p, rng):
@@ -143,8 +155,9 @@ def _check(q, k, v, heads, mask, dropout_p, rng_state):
 
 
 def fused_attention(q, k, v, heads, mask=None, dropout_p=0.0, rng_state=None):
-    """q [B,Nq,H*64], k and v [B,Nk,H*64] (any row stride, e.g. the chunk views of a to_kv output), mask [B,Nk] (False / 0: the
-    key's score is -finfo.max) -> [B,Nq,H*64].  rng_state: int64 device tensor (seed, offset), read by the kernels."""
+    """q [B,Nq,H*64], k and v [B,Nk,H*64] (any layout: read in place where the library can, e.g. the chunk views of a to_kv output,
+    copied otherwise, see _by_stride), mask [B,Nk] or [B,1,Nk] of any type (False / 0: the key's score is -finfo.max)
+    -> [B,Nq,H*64].  rng_state: int64 device tensor (seed, offset), read by the kernels."""
     heads, mask, dropout_p, rng_state = _check(q, k, v, heads, mask, dropout_p, rng_state)
     return _FusedAttention.apply(q, None, k, v, heads, mask, dropout_p, rng_state)
 

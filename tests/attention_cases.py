@@ -41,6 +41,25 @@ CASES = {
                                rng=(0x1234567887654321, 0x100000003)),
     "dropout_p50_masked": dict(B=1, H=2, Nq=70, Nk=130, qd=16, cd=16, scale=1.0, p=0.5, mask="some",
                                rng=(20240229, 7)),
+    # (appended: make_inputs seeds by position.)  The first four reach the four-wave launch form (launch_form below; width 8
+    # keeps their files under the size limit), the last three the key tiles that are masked as a whole.
+    "wide_ragged":         dict(B=16, H=8, Nq=70, Nk=130, qd=8, cd=8, scale=1.0, p=0.0, mask=None),
+    "wide_fwd_narrow_dkv": dict(B=16, H=8, Nq=70, Nk=40, qd=8, cd=8, scale=1.0, p=0.0, mask=None),
+    "narrow_fwd_wide_dkv": dict(B=16, H=8, Nq=40, Nk=70, qd=8, cd=8, scale=1.0, p=0.0, mask=None),
+    "wide_masked_dropout": dict(B=16, H=8, Nq=70, Nk=130, qd=8, cd=8, scale=1.0, p=0.25, mask="b_mod_4",
+                                rng=(0x0F1E2D3C4B5A6978, 0x200000005)),
+    "first_tiles_masked":  dict(B=2, H=2, Nq=20, Nk=130, qd=16, cd=16, scale=1.0, p=0.0, mask="b0_0_63_b1_0_127"),
+    "last_tiles_masked":   dict(B=2, H=2, Nq=20, Nk=130, qd=16, cd=16, scale=1.0, p=0.0, mask="b0_64_on_b1_all_but_129"),
+    "all_masked_dropout":  dict(B=2, H=2, Nq=20, Nk=130, qd=16, cd=16, scale=1.0, p=0.5, mask="b0_60_69_b1_all",
+                                rng=(0xC0FFEE, 0x1FFFFFFFF)),
+}
+
+# The launch form each appended case is there to reach: (forward and dQ, dK/dV), "wide" = four waves per workgroup.
+# tests/test_attention.py restates the library's launch rule from the constants of mgs_attention.hip and asserts this table.
+LAUNCH_FORMS = {
+    "wide_ragged": ("wide", "wide"), "wide_fwd_narrow_dkv": ("wide", "narrow"), "narrow_fwd_wide_dkv": ("narrow", "wide"),
+    "wide_masked_dropout": ("wide", "wide"), "first_tiles_masked": ("narrow", "narrow"),
+    "last_tiles_masked": ("narrow", "narrow"), "all_masked_dropout": ("narrow", "narrow"),
 }
 
 
@@ -81,18 +100,37 @@ def keep_mask(seed, offset, BH, Nq, Nk, p):
 
 
 # ---- inputs ------------------------------------------------------------------------------------------------------------------
-def case_mask(case):
-    c = CASES[case]
-    if c["mask"] is None:
-        return None
-    m = torch.ones(c["B"], c["Nk"], dtype=torch.bool)
-    if c["mask"] == "b0_10_39_b1_all":
+def mask_pattern(name, B, Nk):
+    """bool [B, Nk], False: masked."""
+    m = torch.ones(B, Nk, dtype=torch.bool)
+    if name == "b0_10_39_b1_all":
         m[0, 10:40] = False
         m[1, :] = False
-    else:  # "some": every third key and a run across a tile boundary
+    elif name == "some":  # every third key and a run across a tile boundary
         m[:, ::3] = False
         m[:, 60:70] = False
+    elif name == "b_mod_4":  # the first key tile; every tile but the first; everything; every third key
+        m[0::4, :64] = False
+        m[1::4, 64:] = False
+        m[2::4, :] = False
+        m[3::4, ::3] = False
+    elif name == "b0_0_63_b1_0_127":  # one and two whole tiles masked, live keys after them
+        m[0, :64] = False
+        m[1, :128] = False
+    elif name == "b0_64_on_b1_all_but_129":  # live keys first, then whole masked tiles; one live key at the ragged end
+        m[0, 64:] = False
+        m[1, :129] = False
+    elif name == "b0_60_69_b1_all":
+        m[0, 60:70] = False
+        m[1, :] = False
+    else:
+        raise KeyError(name)
     return m
+
+
+def case_mask(case):
+    c = CASES[case]
+    return None if c["mask"] is None else mask_pattern(c["mask"], c["B"], c["Nk"])
 
 
 def make_inputs(case):

@@ -1,7 +1,9 @@
 """Writes tests/golden/attention/<case>.npz from ManiGaussian's own Attention class (perceiver_lang_io.py:102-145), loaded
 unmodified and run on the CPU in float32 and float64 (tests/attention_cases.py: reference_case).  Arrays only; every file at
 most 1 000 000 bytes.  Run from the repository root on a machine that holds the reference:
-    python tests/golden/make_golden_attention.py
+    python tests/golden/make_golden_attention.py [case ...]
+Without arguments only the files that do not exist yet are written: a committed fixture stays byte for byte what it is (the
+float64 sums of another CPU may differ in the last bits, and so would the compressed file).  Name a case to write it anew.
 tests/test_attention.py::test_fixtures_match_the_reference re-runs this computation against the committed files."""
 import os
 import sys
@@ -16,7 +18,10 @@ import attention_cases as ac  # noqa: E402
 def main():
     assert ac.have_reference(), f"{ac.REF_FILE} not found"
     os.makedirs(ac.GOLDEN_DIR, exist_ok=True)
-    for case in ac.CASES:
+    unknown = [c for c in sys.argv[1:] if c not in ac.CASES]
+    assert not unknown, f"no such case: {unknown}"
+    cases = sys.argv[1:] or [c for c in ac.CASES if not os.path.exists(ac.fixture_path(c))]
+    for case in cases:
         arrays = ac.reference_case(case)
         path = ac.fixture_path(case)
         np.savez_compressed(path, **arrays)

@@ -15,6 +15,7 @@ import ctypes
 import json
 import math
 import os
+import re
 import subprocess
 import sys
 
@@ -27,6 +28,7 @@ import attention_cases as ac
 gpu = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DROPOUT_CASES = [c for c in ac.CASES if ac.CASES[c]["p"] > 0]
+WIDE_SHAPE = (16, 8, 70, 130)  # B, H, Nq, Nk of wide_ragged: four waves per workgroup; one batch item of it: one wave
 FULL = {"encoder_cross": (1, 2048, 8077), "latent_self": (8, 2048, 2048), "decoder_cross": (1, 8077, 2048)}  # H, Nq, Nk
 
 
@@ -136,6 +138,80 @@ def test_the_library_refuses_bad_arguments_before_any_launch():
     assert L.mgs_attention_forward(ctypes.byref(big), fake, fake, None) == INV and "row strides" in _lib.last_error()
 
 
+def test_the_library_refuses_more_than_65535_batch_heads():
+    """B H is the grid's y extent.  65536 is refused by every entry point; 65535 passes that check (and is refused by the next
+    one, for the dropout without a state, before any launch)."""
+    from manigaussian_amd import _lib
+    L = _lib.lib()
+    fake = 0x10000
+    INV = _lib.MGS_ERR_INVALID_ARG
+
+    def calls(a):
+        ws = 1 << 40
+        yield "forward", L.mgs_attention_forward(ctypes.byref(a), fake, fake, None)
+        yield "backward", L.mgs_attention_backward(ctypes.byref(a), fake, fake, fake, fake, fake, fake, ws, None)
+        yield "dropout_mask", L.mgs_attention_dropout_mask(ctypes.byref(a), fake, None)
+
+    def args(B, H, **kw):
+        return _args(H=H, B=B, **kw)
+
+    for B, H in ((65536, 1), (1, 65536), (256, 256)):
+        for p in (0.0, 0.5):
+            a = args(B, H, dropout_p=p)
+            for name, rc in calls(a):
+                assert rc == INV and "B H <= 65535" in _lib.last_error(), (B, H, p, name, rc, _lib.last_error())
+    for B, H in ((65535, 1), (1, 65535), (255, 257)):
+        a = args(B, H, dropout_p=0.5)
+        for name, rc in calls(a):
+            assert rc == INV and "rng_state" in _lib.last_error() and "65535" not in _lib.last_error(), \
+                (B, H, name, rc, _lib.last_error())
+
+
+def _kernel_constants():
+    with open(os.path.join(ROOT, "manigaussian_amd", "csrc", "mgs_attention.hip")) as f:
+        src = f.read()
+    found = dict(re.findall(r"^constexpr int (ATT_\w+) = (\d+);", src, flags=re.M))
+    return {k: int(found[k]) for k in ("ATT_CUS", "ATT_T", "ATT_WQ")}
+
+
+def launch_form(B, H, rows):
+    """mgs_attention.hip's wide(): four waves per workgroup once B H ceil(rows / (4 ATT_WQ)) reaches ATT_CUS workgroups; rows
+    is Nq for the forward and dQ, Nk for dK/dV."""
+    k = _kernel_constants()
+    per_wg = 4 * k["ATT_WQ"]
+    return "wide" if B * H * ((rows + per_wg - 1) // per_wg) >= k["ATT_CUS"] else "narrow"
+
+
+def test_the_wide_cases_reach_the_four_wave_form():
+    """The premise of the cases appended for the 256-thread form, pinned: a change of the launch rule fails here instead of
+    quietly turning them into one-wave runs."""
+    k = _kernel_constants()
+    assert k["ATT_T"] == 4 * k["ATT_WQ"] == 64, "the cases' tile edges (64, 128) and ragged ends assume 64-row tiles"
+    assert set(ac.LAUNCH_FORMS) == set(list(ac.CASES)[10:])
+    for case, (fwd, dkv) in ac.LAUNCH_FORMS.items():
+        c = ac.CASES[case]
+        assert launch_form(c["B"], c["H"], c["Nq"]) == fwd, (case, "forward and dQ")
+        assert launch_form(c["B"], c["H"], c["Nk"]) == dkv, (case, "dK/dV")
+    assert all(launch_form(c["B"], c["H"], max(c["Nq"], c["Nk"])) == "narrow" for c in list(ac.CASES.values())[:10])
+    # wide_ragged's last workgroups: 6 live queries and 2 live keys in wave 0, none in waves 1 to 3
+    c = ac.CASES["wide_ragged"]
+    assert c["Nq"] % 64 == 6 and c["Nk"] % 64 == 2
+    # test_four_wave_and_one_wave_launches_give_the_same_bits: the batch is wide in both directions, one item of it is not
+    B, H, Nq, Nk = WIDE_SHAPE
+    assert launch_form(B, H, Nq) == launch_form(B, H, Nk) == "wide"
+    assert launch_form(1, H, Nq) == launch_form(1, H, Nk) == "narrow"
+    # the masks are what the cases' names say: whole 64-key tiles
+    m = ac.case_mask("first_tiles_masked")
+    assert not m[0, :64].any() and m[0, 64:].all() and not m[1, :128].any() and m[1, 128:].all()
+    m = ac.case_mask("last_tiles_masked")
+    assert m[0, :64].all() and not m[0, 64:].any() and m[1].nonzero().flatten().tolist() == [129]
+    m = ac.case_mask("all_masked_dropout")
+    assert m[0].sum() == 120 and not m[1].any()
+    m = ac.case_mask("wide_masked_dropout")
+    assert not m[0, :64].any() and m[0, 64:].all() and m[1, :64].all() and not m[1, 64:].any() and not m[2].any()
+    assert m[3].tolist() == [j % 3 != 0 for j in range(130)] and torch.equal(m[:4], m[12:])
+
+
 def test_the_workspace_size_is_monotone_and_aligned():
     from manigaussian_amd import _lib
     W = _lib.lib().mgs_attention_workspace_bytes
@@ -222,12 +298,19 @@ def test_every_fixture_forward_and_backward(case):
             bad.append((n, err, bound))
     record("fixture/" + case, rows)
     assert not bad, (case, bad)
-    if case == "masked":  # the reference's edge case: a row whose keys are all masked attends uniformly (the mean of v)
-        m = build_module(case)
-        kv = m.to_kv(f["context"].to(dev()))
-        v = kv.chunk(2, dim=-1)[1][1]
-        exp = m.to_out(v.mean(0, keepdim=True)).expand(9, -1)
-        assert (got["out"][1] - exp.detach().cpu()).abs().max().item() <= 1e-6 * exp.abs().max().item() + 1e-7
+    # the reference's edge case: a row whose keys are all masked attends uniformly; without dropout it is the mean of v
+    dead = [] if "mask" not in f else [b for b in range(f["mask"].size(0)) if not f["mask"][b].any()]
+    assert dead == {"masked": [1], "wide_masked_dropout": [2, 6, 10, 14], "all_masked_dropout": [1]}.get(case, [])
+    if dead:
+        m = build_module(case).eval()  # (eval: no dropout)
+        with torch.no_grad():
+            out = m(f["x"].to(dev()), context=f["context"].to(dev()), mask=f["mask"].to(dev())).cpu()
+            v = m.to_kv(f["context"].to(dev())).chunk(2, dim=-1)[1]
+            exp = m.to_out(v.mean(1, keepdim=True)).expand(-1, ac.CASES[case]["Nq"], -1).cpu()
+        for b in dead:
+            d, lim = (out[b] - exp[b]).abs().max().item(), 1e-6 * exp[b].abs().max().item() + 1e-7
+            print(f"{case} item {b}, all keys masked: |out - to_out(mean v)| {d:.3e}, allowed {lim:.3e}")
+            assert d <= lim, (case, b, d, lim)
 
 
 @gpu
@@ -282,6 +365,174 @@ def test_strided_inputs_equal_contiguous_copies_bit_for_bit(p):
     out.backward(g)
     assert kv_.grad.is_contiguous() and ac.same_bits(out.detach().cpu(), base[0].cpu())
     assert ac.same_bits(kv_.grad.cpu(), torch.cat([base[2], base[3]], dim=-1).cpu())
+
+
+def _run_qkv(q_, k_, v_, H, g, p=0.0, state=None, mask=None, backward=None):
+    """out and the gradients of q, k, v, which are taken as they are laid out (detach keeps strides and offset)."""
+    from manigaussian_amd import fused_attention
+    q_, k_, v_ = (t.detach().requires_grad_(True) for t in (q_, k_, v_))
+    out = fused_attention(q_, k_, v_, H, mask=mask, dropout_p=p, rng_state=state)
+    if backward is None:
+        out.backward(g)
+    else:
+        backward(out)
+    return out.detach(), q_.grad, k_.grad, v_.grad
+
+
+def _assert_same(base, other, what):
+    for n, a, b in zip(("out", "dq", "dk", "dv"), base, other):
+        assert a.shape == b.shape and ac.same_bits(a.cpu(), b.cpu()), (what, n)
+
+
+def _odd_layouts(t):
+    """t [B,N,W] in layouts the library does not read in place: base not 16-byte aligned; row stride no multiple of 4 floats."""
+    B, N, W = t.shape
+    off = torch.zeros(B, N, W + 4, device=t.device)
+    off[..., 1:1 + W] = t
+    odd = torch.zeros(B, N, W + 2, device=t.device)
+    odd[..., :W] = t
+    views = {"misaligned": off[..., 1:1 + W], "odd_row_stride": odd[..., :W]}
+    assert views["misaligned"].data_ptr() % 16 == 4 and views["odd_row_stride"].stride(1) % 4 == 2
+    assert all(torch.equal(v, t) and v.stride(2) == 1 for v in views.values())
+    return views
+
+
+@gpu
+@pytest.mark.parametrize("p", [0.0, 0.2])
+def test_layouts_the_library_refuses_are_copied_and_equal_contiguous_copies_bit_for_bit(p):
+    """fused_attention / fused_attention_kv take any layout with a unit last stride; where mgs_attention_forward / _backward
+    would refuse it (base not 16-byte aligned, row stride no multiple of 4 or shorter than the row) the wrapper copies."""
+    from manigaussian_amd.attention import fused_attention_kv
+    B, H, Nq, Nk = 2, 2, 70, 150
+    HD = H * 64
+    q, kv, g = _qkv(B, H, Nq, Nk, 3)
+    state = torch.tensor([11, 5], dtype=torch.int64, device=dev()) if p else None
+    k, v = (t.contiguous() for t in kv.chunk(2, dim=-1))
+    base = _run_qkv(q, k, v, H, g, p, state)
+    for name, view in _odd_layouts(q).items():
+        _assert_same(base, _run_qkv(view, k, v, H, g, p, state), "q " + name)
+    for (name, kview), vview in zip(_odd_layouts(k).items(), _odd_layouts(v).values()):
+        _assert_same(base, _run_qkv(q, kview, vview, H, g, p, state), "k and v " + name)
+        _assert_same(base, _run_qkv(q, kview, v, H, g, p, state), "k " + name)
+        _assert_same(base, _run_qkv(q, k, vview, H, g, p, state), "v " + name)
+    # q expanded over the batch (batch stride 0) and over the rows (row stride 0); the gradient has q's shape
+    for name, src in (("batch", q[:1]), ("rows", q[:, :1])):
+        view = src.expand(B, Nq, HD)
+        assert view.stride(0 if name == "batch" else 1) == 0
+        _assert_same(_run_qkv(view.contiguous(), k, v, H, g, p, state), _run_qkv(view, k, v, H, g, p, state),
+                     "q expanded over the " + name)
+    # upstream gradients of row stride 0: what out.sum(1).backward(g2) sends, strides (HD, 0, 1), and (0, 0, 1)
+    g2 = g[:, 0].contiguous()
+    seen = []
+
+    def summed(out):
+        out.register_hook(lambda d: seen.append(d.stride()))
+        out.sum(1).backward(g2)
+
+    _assert_same(_run_qkv(q, k, v, H, g2[:, None].expand(B, Nq, HD).contiguous(), p, state),
+                 _run_qkv(q, k, v, H, None, p, state, backward=summed), "d_out from sum(1)")
+    assert seen == [(HD, 0, 1)], seen
+    g1 = g[0, 0].contiguous()
+    _assert_same(_run_qkv(q, k, v, H, g1.expand(B, Nq, HD).contiguous(), p, state),
+                 _run_qkv(q, k, v, H, g1.expand(B, Nq, HD), p, state), "d_out of strides (0, 0, 1)")
+    # the packed form with kv as a misaligned slice of a wider buffer
+    for name, view in _odd_layouts(kv).items():
+        q_, kv_ = q.detach().requires_grad_(True), view.detach().requires_grad_(True)
+        out = fused_attention_kv(q_, kv_, H, dropout_p=p, rng_state=state)
+        out.backward(g)
+        assert kv_.grad.shape == kv.shape
+        _assert_same(base, (out.detach(), q_.grad, kv_.grad[..., :HD], kv_.grad[..., HD:]), "kv " + name)
+
+
+@gpu
+def test_layouts_the_library_accepts_are_not_copied(monkeypatch):
+    """The aligned column slice and the chunk halves of test_strided_inputs_..., the packed kv, a batch-expanded q and a
+    contiguous gradient reach the library where they lie: the wrapper's copy is never taken, forward or backward."""
+    from manigaussian_amd import attention
+    B, H, Nq, Nk = 2, 2, 70, 150
+    HD = H * 64
+    q, kv, g = _qkv(B, H, Nq, Nk, 3)
+    wide = torch.zeros(B, Nq, HD + 64, device=dev())
+    wide[..., 32:32 + HD] = q
+    k, v = kv.chunk(2, dim=-1)
+    base = _run_qkv(q, k.contiguous(), v.contiguous(), H, g)
+    copies = []
+    real = attention._copy
+
+    def probe(t):
+        copies.append((tuple(t.shape), t.stride()))
+        return real(t)
+
+    monkeypatch.setattr(attention, "_copy", probe)
+    _assert_same(base, _run_qkv(wide[..., 32:32 + HD], k, v, H, g), "aligned slice, chunk halves")
+    _assert_same(_run_qkv(q[:1].expand(B, Nq, HD).contiguous(), k, v, H, g), _run_qkv(q[:1].expand(B, Nq, HD), k, v, H, g),
+                 "q expanded over the batch")
+    q_, kv_ = q.detach().requires_grad_(True), kv.detach().requires_grad_(True)
+    out = attention.fused_attention_kv(q_, kv_, H)
+    out.backward(g)
+    _assert_same(base, (out.detach(), q_.grad, kv_.grad[..., :HD], kv_.grad[..., HD:]), "packed kv")
+    assert copies == [], copies
+    _run_qkv(wide[..., 1:1 + HD], k, v, H, g)
+    assert copies == [((B, Nq, HD), (Nq * (HD + 64), HD + 64, 1))], "(the probe sees a copy when there is one)"
+
+
+def _wide_mask():
+    B, H, Nq, Nk = WIDE_SHAPE
+    return ac.mask_pattern("b_mod_4", B, Nk).to(dev())
+
+
+@gpu
+@pytest.mark.parametrize("masked", [False, True])
+def test_four_wave_and_one_wave_launches_give_the_same_bits(masked):
+    """"a wave's arithmetic does not depend on its workgroup".  The batch of 16 is launched with four waves per
+    workgroup (256 and 384 workgroups), one item of it with one wave (test_the_wide_cases_reach_the_four_wave_form); p = 0,
+    because the dropout's counter holds b H + h."""
+    from manigaussian_amd.attention import fused_attention_kv
+    B, H, Nq, Nk = WIDE_SHAPE
+    q, kv, g = _qkv(B, H, Nq, Nk, 29)
+    mask = _wide_mask() if masked else None
+
+    def run(sl):
+        q_, kv_ = q[sl].detach().requires_grad_(True), kv[sl].detach().requires_grad_(True)
+        out = fused_attention_kv(q_, kv_, H, mask=None if mask is None else mask[sl])
+        out.backward(g[sl])
+        return out.detach().cpu(), q_.grad.cpu(), kv_.grad.cpu()
+
+    whole = run(slice(None))
+    for t in whole:
+        assert bool(torch.isfinite(t).all())
+    for b in (0, 5, 10, 15):
+        for n, w, o in zip(("out", "dq", "dkv"), whole, run(slice(b, b + 1))):
+            assert ac.same_bits(w[b:b + 1], o), (b, n)
+
+
+@gpu
+def test_every_form_of_the_mask_gives_the_same_bits():
+    """_check's paths: a mask of another type (non-zero: live), of shape [B,1,Nk], and a non-contiguous column slice."""
+    from manigaussian_amd.attention import fused_attention_kv
+    c, f = ac.CASES["masked"], ac.load_fixture("masked")
+    B, H, Nq, Nk = c["B"], c["H"], c["Nq"], c["Nk"]
+    q, kv, g = _qkv(B, H, Nq, Nk, 31)
+    mask = f["mask"].to(dev())
+    assert mask.dtype == torch.bool and mask.shape == (B, Nk)
+
+    def run(m):
+        q_, kv_ = q.detach().requires_grad_(True), kv.detach().requires_grad_(True)
+        out = fused_attention_kv(q_, kv_, H, mask=m)
+        out.backward(g)
+        return out.detach().cpu(), q_.grad.cpu(), kv_.grad.cpu()
+
+    base = run(mask)
+    assert not ac.same_bits(base[0], run(None)[0]), "the mask must matter"
+    wider = torch.ones(B, Nk + 7, dtype=torch.bool, device=dev())
+    wider[:, 3:3 + Nk] = mask
+    sliced = wider[:, 3:3 + Nk]
+    assert not sliced.is_contiguous()
+    forms = {"uint8": mask.to(torch.uint8), "int64": mask.to(torch.int64) * 3, "float32": mask.to(torch.float32),
+             "bool [B,1,Nk]": mask[:, None, :], "column slice": sliced, "uint8 [B,1,Nk] column slice": sliced[:, None, :].to(torch.uint8)}
+    for name, m in forms.items():
+        for n, a, b in zip(("out", "dq", "dkv"), base, run(m)):
+            assert ac.same_bits(a, b), (name, n)
 
 
 @gpu

@@ -76,6 +76,8 @@ typedef struct MgsOptions {
                              0x7000   bits 12-14 = 1 + log2 of the bucket rank's parts per tile (0: chosen by the tile count)
                              32768    direct binning off: the bin scatter launch writes the tile keys
                              1 << 16  render backward (12 waves): the extra chunks 8, 9 are not split between two waves
+                             1 << 17  render forward: every chunk of a round is evaluated ahead of the round's one barrier
+                                      (default: the chunks of the second slot only as far as a pixel is alive entering them)
                            512 and 1024 reach the forward preprocess only; a forward retried after a hand-shake give-up
                            runs without them                                                                               */
   int32_t table_init;   /* 0*: the forward preprocess launch zeroes its own tile tables (workgroup 0 + a bounded hand-shake:

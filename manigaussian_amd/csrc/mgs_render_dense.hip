@@ -42,7 +42,8 @@ __device__ unsigned long long g_trace[512 * 16 * TRACE_EVENTS];
 //     transposition per chunk;
 //   * twice the live waves per block, each with a quarter of the instructions.
 // A pair blends up to NS = 2 chunks per round (chunks pr and pr + NW/2), so a round still covers NW chunks: blocks whose
-// pixels need more than NW/2 chunks (15 % of them at configs[2]) do not pay a second fill / barrier round.
+// pixels need more than NW/2 chunks (15 % of them at configs[2]) do not pay a second fill / barrier round.  The second
+// chunks are staged and evaluated only as far as some pixel is alive entering them (the stages of a round, below).
 // Per-pixel results are those of the reference's walk: same alpha expression, same test order, same sequential T chain.
 // TWO: two workgroups of this kernel share a CU (8 waves, <= 128 registers, <= 80 KB of LDS each)
 template <int F, bool FAST, bool EXACT, int NW, int CHS, bool TWO>
@@ -108,6 +109,7 @@ coop_fwd_pairs_kernel(RenderArgs r, const uint2* __restrict__ ranges, const uint
   const bool insidex = pix_blk(r, tile, sub, pixx).inside; // k = 0 lanes their own, k = 1 lanes the other half's (64 in all)
   const uint2 rng = ranges[tile];
   const bool use_feat = (F > 0) && r.include_feature;
+  const bool eager = (r.dbg & (1 << 17)) != 0;   // (grid-uniform) A/B: every chunk of a round evaluated ahead of its one barrier
   // the feature table as a buffer resource (wave-uniform: kernel argument); rows are addressed by 32-bit byte offsets, which
   // the host side guarantees to fit (mgs_api.hip: P F 4 < 2^32)
   const auto feat_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(r.feats), 0, 0xffffffffu, 0x00020000);
@@ -234,20 +236,22 @@ coop_fwd_pairs_kernel(RenderArgs r, const uint2* __restrict__ ranges, const uint
       const float a0 = fminf(0.99f, oG.x), a1 = fminf(0.99f, oG.y);
       return f32x2{((power.x > 0.0f) || (a0 < 1.0f / 255.0f)) ? 0.f : a0, ((power.y > 0.0f) || (a1 < 1.0f / 255.0f)) ? 0.f : a1};
     };
-    auto alpha2_of = [&](uint32_t buf, int j) -> f32x2 { return alpha2_rec(rec3_of(buf, j)); };
-    float al[NSTEP];          // the alphas of my FIRST chunk stay in registers: its blend evaluates no exp.  (The second
-                              // chunk of a round -- blocks with more than NW/2 live chunks -- is staged last, so its records
-                              // are still in recP when it is blended: its alphas are evaluated again there.)
+    float al[NSTEP];          // the alphas of the chunk I blend next stay in registers: the blend evaluates no exp
+                              // (written by a stage's phase A for its phase B: nothing is carried from stage to stage)
     uint32_t nmy[NS];         // survivors of my chunks
 #pragma unroll
     for (int q = 0; q < NS; q++) {
       const uint32_t ci = (uint32_t)pr + (uint32_t)q * NP;
+      nmy[q] = ci < nchunk ? min((uint32_t)CHS, avail - ci * CHS) : 0u;
+    }
+    // Phase A of my chunk of slot q: its rows are staged, its alphas go to al[].  q and publish are wave-uniform.  publish: the
+    // product goes to Tp -- false where it is there already and only the alphas are wanted again (the eager form's second
+    // slot; its rows are then staged a second time, the same values: a run-time switch around the staging costs every form
+    // ~500 bytes of scratch per lane, the LDS reads of all steps are then issued at once).  ONE copy of this code and one
+    // of phase B serve both slots: each is called from one place, see the stages below.
+    auto phase_a = [&](const int q, const bool publish) __attribute__((always_inline)) {
+      const uint32_t ci = (uint32_t)pr + (uint32_t)q * NP;
       const bool hasq = ci < nchunk;  // wave-uniform
-      nmy[q] = hasq ? min((uint32_t)CHS, avail - ci * CHS) : 0u;
-      if (q == 0) {
-#pragma unroll
-        for (int s = 0; s < NSTEP; s++) al[s] = 0.f;
-      }
       float tp = 1.0f;
       if (hasq) {
         // lane e stages entry e of the chunk: its record (round 0: already in place, see the fill), its colour row
@@ -255,7 +259,7 @@ coop_fwd_pairs_kernel(RenderArgs r, const uint2* __restrict__ ranges, const uint
         float fv[NVF > 0 ? NVF : 1];
 #pragma unroll
         for (int i = 0; i < (NVF > 0 ? NVF : 1); i++) fv[i] = 0.f;
-        const bool valid = (uint32_t)lane < nmy[q];
+        const bool valid = (uint32_t)lane < (q ? nmy[1] : nmy[0]);
         float* rp = reinterpret_cast<float*>(&recP[ci][0]) + (((lane >> 2) * 2 + (lane & 1)) * 12 + ((lane >> 1) & 1));
         // instance id -> Gaussian row (block-uniform), derived from the tile where it is used: held in an SGPR across the
         // rounds it adds scalar spills to the wide kernels
@@ -309,7 +313,7 @@ coop_fwd_pairs_kernel(RenderArgs r, const uint2* __restrict__ ranges, const uint
           const Rec3 Rc = Rn;
           if (j + 1 < NSTEP / 2) Rn = rec3_of(ci, j + 1);
           const f32x2 a2 = alpha2_rec(Rc);
-          if (q == 0) { al[2 * j] = a2.x; al[2 * j + 1] = a2.y; }
+          al[2 * j] = a2.x; al[2 * j + 1] = a2.y;
           tp2 = tp2 * (1.0f - a2);
         }
         tp = tp2.x * tp2.y;
@@ -323,39 +327,19 @@ coop_fwd_pairs_kernel(RenderArgs r, const uint2* __restrict__ ranges, const uint
         swap32(t0, t1);       // t0: the even entries' product, t1: the odd entries', in both lanes of the pixel
         tp = t0 * t1;
       }
-      if (k == 0) Tp[round & 1][ci][pixq] = tp;  // (1 for a chunk slot the round does not use)
-    }
-    MGS_TRACE(4 + 8 * round);
-    __syncthreads();
-    // every load of this round so far has been consumed; saying so (s_waitcnt vmcnt(0), free here) keeps the compiler from
-    // protecting registers it believes still awaited further down -- behind this round's stores, whose drain that wait would
-    // then include (one in-order counter for loads and stores)
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-    MGS_TRACE(5 + 8 * round);
-    const uint32_t rb = rbase[round & 1];
-    if (rb + (uint32_t)NW > pool) { overflow = true; break; }  // uniform: every thread reads the same word
-    // ---- prefix in chunk order (identical arithmetic in every wave): transmittance of pixel pixx entering my chunks ----
-    float Tin[NS], Tnext = Tround;
-#pragma unroll
-    for (int q = 0; q < NS; q++) Tin[q] = Tround;
-#pragma unroll
-    for (int c2 = 0; c2 < NW; c2++) {
-      const float t2 = Tp[round & 1][c2][pixx];
-#pragma unroll
-      for (int q = 0; q < NS; q++) Tin[q] = (c2 < pr + q * NP) ? Tin[q] * t2 : Tin[q];
-      Tnext *= t2;
-    }
-    // ---- phase B: blend my chunks ----
-#pragma unroll
-    for (int q = 0; q < NS; q++) {
+      if (publish && k == 0) Tp[round & 1][ci][pixq] = tp;  // (1 for a chunk slot the round does not use)
+    };
+    uint32_t rb = 0;  // first chunk record of the round (pool index), read behind the round's barrier
+    // ---- phase B: blend my chunk of slot q from al[]; Tin_q: the transmittance of pixel pixx entering it ----
+    auto phase_b = [&](const int q, const float Tin_q) __attribute__((always_inline)) {
       const uint32_t ci = (uint32_t)pr + (uint32_t)q * NP;
       const bool hasq = ci < nchunk;
       // the k = 1 lanes tracked the other half's pixel: they take my pixel's transmittance from their k = 0 partner
-      const float Tpart = __uint_as_float(lane_xor<32>(__float_as_uint(Tin[q]), lane));
-      float T = k ? Tpart : Tin[q];
+      const float Tpart = __uint_as_float(lane_xor<32>(__float_as_uint(Tin_q), lane));
+      float T = k ? Tpart : Tin_q;
       const bool live = hasq && pq.inside && !(T < 0.0001f);
       if (ballot(live) != 0) {
-        const uint32_t n_my = nmy[q];
+        const uint32_t n_my = q ? nmy[1] : nmy[0];
         float Cc[3] = {0.f, 0.f, 0.f};
         float Cv[NVF > 0 ? NVF : 1];
 #pragma unroll
@@ -404,12 +388,10 @@ coop_fwd_pairs_kernel(RenderArgs r, const uint2* __restrict__ ranges, const uint
           stop = stop || (uint32_t)(2 * g * GS) >= n_my || ballot(Tc != 0.f) == 0;
           __builtin_amdgcn_sched_barrier(0);
           if (!stop) {
-            f32x2 a2q = {0.f, 0.f};  // the second chunk's alphas of a double step (evaluated at its even step)
 #pragma unroll
             for (int u4 = 0; u4 < GS; u4++) {
               const int s = g * GS + u4;
-              if (q != 0 && (u4 & 1) == 0) a2q = alpha2_of(ci, s >> 1);
-              float a0 = (q == 0) ? al[s] : ((u4 & 1) ? a2q.y : a2q.x), a1 = a0;
+              float a0 = al[s], a1 = a0;
               swap32(a0, a1);  // a0 = alpha of entry 2s, a1 = alpha of entry 2s + 1 for my pixel, in both of its lanes
               // two entries of the reference's per-pixel walk (forward.cu:357-380).  A live pixel always has T >= 1e-4 (it
               // entered so, and a blend only happens when the new T stays above), hence alpha == 0 (a skipped entry) can
@@ -497,7 +479,64 @@ coop_fwd_pairs_kernel(RenderArgs r, const uint2* __restrict__ ranges, const uint
         }
         if (live) { my_vis = cbase + ci + 1; my_Tf = T; }
       }
+    };
+    // ---- The round, in stages.  Slot 0 first (stage 0): phase A of chunks 0 .. NP - 1, the barrier, the prefix, their blend.
+    //      Slot 1 only as far as a pixel reaches it: chunk NP + j is evaluated while some pixel is alive entering it.  At
+    //      BASELINE configs[2] the fill hands nearly every block NW chunks, 85 % of the blocks blend at most NP of them and none
+    //      more than 10.  Every wave tracks all 64 pixels from the same LDS values with the same arithmetic, so each decision
+    //      is workgroup-uniform without any communication.  The slot goes in two groups of pairs, the first GA chunks (stage 1)
+    //      and the rest (stage 2), each with one barrier behind which the group's products are read; the pairs of a group
+    //      blend while the next group's evaluate.  A group that no pixel reaches costs nothing: no staging, no row requests, no
+    //      alphas, no barrier; its products count as 1 (transmittance never increases: Tnext stays below 1e-4 everywhere and
+    //      the rounds end).  The prefix continues the same left-to-right product, so every pixel that is alive anywhere sees
+    //      the bits it saw when all NW chunks were evaluated up front.
+    //      eager (MgsOptions.dbg & 1 << 17, grid-uniform; the A/B reference): every chunk of the round is evaluated ahead of
+    //      the one barrier (stage -1: slot 1's products), and a second chunk's alphas are formed again before its
+    //      blend. ----
+    constexpr int GA = 2;
+    static_assert(GA < NP, "slot 1 goes in two groups of pairs");
+    float Tnext = Tround;
+    int p0 = 0, p1 = NP;  // the pairs of the stage
+#pragma clang loop unroll(disable)
+    for (int st = eager ? -1 : 0;; st++) {
+      // (as at the top of a round: without it the address arithmetic below is hoisted out of this loop and spilled)
+      asm volatile("" : "+v"(k), "+v"(pl), "+v"(pixq), "+v"(pixx));
+      const int q = st == 0 ? 0 : 1;
+      const bool act = pr >= p0 && pr < p1;  // wave-uniform
+#pragma unroll
+      for (int s = 0; s < NSTEP; s++) al[s] = 0.f;
+      if (act) {
+        phase_a(q, st <= 0 || !eager);
+        if (st > 0) MGS_TRACE(8 + 8 * round);  // (and with it: how many waves evaluated a second chunk behind the barrier)
+      }
+      if (st < 0) continue;
+      if (st == 0) MGS_TRACE(4 + 8 * round);
+      if (st == 0 || !eager) __syncthreads();
+      if (st == 0) {
+        // every load of this round so far has been consumed; saying so (s_waitcnt vmcnt(0), free here) keeps the compiler from
+        // protecting registers it believes still awaited further down -- behind this round's stores, whose drain that wait
+        // would then include (one in-order counter for loads and stores)
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+        MGS_TRACE(5 + 8 * round);
+        rb = rbase[round & 1];
+        if (rb + (uint32_t)NW > pool) { overflow = true; break; }  // uniform: every thread reads the same word
+      }
+      // prefix in chunk order (identical arithmetic in every wave) over the stage's chunks: the transmittance of pixel pixx
+      // entering my chunk, and after the stage's last one
+      float Tin = Tnext;
+#pragma unroll
+      for (int c2 = 0; c2 < NP; c2++) {
+        const float t2 = (c2 >= p0 && c2 < p1) ? Tp[round & 1][q * NP + c2][pixx] : 1.0f;  // (another group's: not written yet, or stale)
+        Tin = (c2 < pr) ? Tin * t2 : Tin;
+        Tnext *= t2;
+      }
+      if (act) phase_b(q, Tin);
+      if (st == 2) break;
+      p0 = st == 0 ? 0 : GA;
+      p1 = st == 0 ? GA : NP;
+      if (!((uint32_t)(NP + p0) < nchunk) || ballot(insidex && !(Tnext < 0.0001f)) == 0) break;
     }
+    if (overflow) break;
     MGS_TRACE(7 + 8 * round);
     Tround = Tnext;
     qhead += min(avail, nchunk * CHS);
@@ -596,17 +635,22 @@ coop_fwd_pairs_kernel(RenderArgs r, const uint2* __restrict__ ranges, const uint
     ticket = atomicAdd(&flags[FLAG_BLOCKS_DONE], 1u + dep) + 1u;
   }
   const size_t HW = (size_t)r.Hv * r.W;  // one image plane of one view
-  if (p.inside) {
+  // the pixel's place in the outputs, derived again here (through an opaque lane: not merged with the copy the fill used): held
+  // across the rounds these indices were spilled in the forms without a spare register
+  int lane_o = lane;
+  asm volatile("" : "+v"(lane_o));
+  const PixBlk po = pix_blk(r, tile, sub, lane_o);
+  if (po.inside) {
 #pragma unroll
     for (int kk = 0; kk < NOWN; kk++) {
       const int ch = w + kk * NW;
-      if (ch < 3) out_color[((size_t)p.v * 3 + ch) * HW + p.pixl] = img[kk] + Tf * r.bg[ch];
-      else if (ch < NCH && use_feat) out_feat[((size_t)p.v * F + (ch - 3)) * HW + p.pixl] = img[kk];
+      if (ch < 3) out_color[((size_t)po.v * 3 + ch) * HW + po.pixl] = img[kk] + Tf * r.bg[ch];
+      else if (ch < NCH && use_feat) out_feat[((size_t)po.v * F + (ch - 3)) * HW + po.pixl] = img[kk];
     }
   }
   if (w == 0) {
     last_chunk[((size_t)tile * 4 + sub) * 64 + lane] = vis;
-    if (p.inside) final_T[p.pixa] = Tf;
+    if (po.inside) final_T[po.pixa] = Tf;
     if (lane == 0) {
       nsurv[(size_t)tile * 4 + sub] = make_uint2(qtail, round > 0 || vis > 0 ? rb_hist[0] : 0u);  // + round 0's first record
       // the workgroup that drew the last ticket reports {tag, overflow, chunk records used} to the host (mapped pinned memory)

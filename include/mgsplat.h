@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 12
+#define MGS_ABI_VERSION 13
 
 /* error codes */
 #define MGS_OK 0
@@ -524,6 +524,40 @@ int mgs_spatial_softmax_forward(int64_t rows, int C, int D, int H, int W, float 
 int mgs_spatial_softmax_backward(int64_t rows, int C, int D, int H, int W, float temperature, const float* feature,
                                  const float* stats, const float* g_keypoints, int64_t g_keypoints_stride_b, const float* g_max,
                                  int64_t g_max_stride_b, float* g_feature, int slices, mgs_stream_t stream);
+
+/* ---- the Perceiver decoder's volume plumbing between its convolutions, fused, fp32 (MG/agents/manigaussian_bc/
+ * perceiver_lang_io.py:488-499; MG/helpers/network_utils.py:129-171 Conv3DBlock, 374-391 Conv3DUpsampleBlock) -- ABI v13 ----
+ *   out = replicate_pad(trilinear_upsample(cat(sources, 1), scale, align_corners = False), pad)
+ * sources: nsrc tensors [B, C_k, D, H, W] whose spatial dimensions are contiguous: element (b, c, z, y, x) of source k lies at
+ * src[k][b stride_b[k] + c stride_c[k] + (z H + y) W + x] (strides in floats, any value: a channel slice of a wider tensor is read
+ * in place).  out [B, sum C_k, s D + 2 p, s H + 2 p, s W + 2 p], contiguous.  Per axis of source length n, for the padded index op:
+ *   o = clamp(op - p, 0, s n - 1);  src = max((o + 0.5) / s - 0.5, 0);  i0 = floor(src);  lambda = src - i0;  i1 = min(i0 + 1, n - 1)
+ * weights 1 - lambda on i0 and lambda on i1, 1 / s and lambda in fp32 (torch's arithmetic); the 3-D weight is the product of the
+ * axes'.  scale == 1 is a copy, bit for bit.
+ * forward: one launch; every element of out is written exactly once, 16 bytes at a time.
+ * backward: g_out [as out], contiguous -> g_src[k] [B, C_k, D, H, W], contiguous, one per source.  A gather: each gradient element
+ * is written once, from the padded outputs that reach it summed in ascending index order; nothing is zero-filled.  scale > 1: two
+ * launches (x and y per padded z-plane into the workspace [B sum C_k, s D + 2 p, H, W], then z); scale == 1: one launch, g_out
+ * read about once.  workspace: at least the workspace-size query's bytes (positive for every valid shape; 0: invalid shape).
+ * MGS_ERR_INVALID_ARG before any launch: scale outside 1..8; pad outside 0..8; nsrc outside 1..4; a C_k < 1; B < 0; D, H or W < 1;
+ * the padded output (hence any source) above 2^31 - 1 elements; a NULL pointer (the arguments, a used src[k], out, g_out, g_src,
+ * a used g_src[k], the workspace); out, a g_src[k] or the workspace not 16-byte aligned, a src[k] or g_out not 4-byte aligned; a
+ * workspace below the query's size.  B == 0: MGS_OK, nothing is launched.  Indices inside a tensor are 32-bit, a source's batch
+ * and channel offsets 64-bit.  Bit-identical from run to run.  No host read, no allocation, no state: capturable into a HIP graph. */
+#define MGS_VOLUME_MAX_SOURCES 4
+#define MGS_VOLUME_MAX_SCALE 8
+#define MGS_VOLUME_MAX_PAD 8
+typedef struct MgsVolumeArgs {
+  int32_t B, D, H, W;      /* batch and the sources' common spatial shape */
+  int32_t scale, pad, nsrc;
+  int32_t C[MGS_VOLUME_MAX_SOURCES];
+  const float* src[MGS_VOLUME_MAX_SOURCES];   /* forward only */
+  int64_t stride_b[MGS_VOLUME_MAX_SOURCES], stride_c[MGS_VOLUME_MAX_SOURCES];
+} MgsVolumeArgs;
+size_t mgs_volume_workspace_bytes(const MgsVolumeArgs* a);
+int mgs_volume_resample_pad_forward(const MgsVolumeArgs* a, float* out, mgs_stream_t stream);
+int mgs_volume_resample_pad_backward(const MgsVolumeArgs* a, const float* g_out, float* const* g_src, void* workspace,
+                                     size_t workspace_bytes, mgs_stream_t stream);
 
 /* Per-stage device timing (hipEvents on the caller's stream), enabled with
  * mgs_set_option("profile", 1) (render backward only) or 2 (every stage).  mgs_profile_read waits for the

@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmgsplat.so")
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 c_fp = ctypes.c_void_p  # device pointers travel as integers (tensor.data_ptr())
 c_i32 = ctypes.c_int32
@@ -56,6 +56,15 @@ class MgsAttentionArgs(ctypes.Structure):
                [(n, ctypes.c_int64) for n in ("q_stride_b", "q_stride_n", "k_stride_b", "k_stride_n", "v_stride_b", "v_stride_n",
                                               "out_stride_b", "out_stride_n", "dout_stride_b", "dout_stride_n", "dq_stride_b",
                                               "dq_stride_n", "dkv_stride_b", "dkv_stride_n", "mask_stride_b")]
+
+
+VOLUME_MAX_SOURCES = 4
+
+
+class MgsVolumeArgs(ctypes.Structure):
+    _fields_ = [("B", c_i32), ("D", c_i32), ("H", c_i32), ("W", c_i32), ("scale", c_i32), ("pad", c_i32), ("nsrc", c_i32),
+                ("C", c_i32 * VOLUME_MAX_SOURCES), ("src", c_fp * VOLUME_MAX_SOURCES),
+                ("stride_b", ctypes.c_int64 * VOLUME_MAX_SOURCES), ("stride_c", ctypes.c_int64 * VOLUME_MAX_SOURCES)]
 
 
 MAX_VIEWS = 16  # views of a batch; also the most Gaussian sets of a set batch
@@ -141,6 +150,9 @@ _EXPORTS = {
                                                    c_fp, ctypes.c_int64, c_fp, c_fp, c_sz, ctypes.c_int, c_fp]),
     "mgs_spatial_softmax_backward": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int] * 4 + [ctypes.c_float, c_fp, c_fp, c_fp,
                                                     ctypes.c_int64, c_fp, ctypes.c_int64, c_fp, ctypes.c_int, c_fp]),
+    "mgs_volume_workspace_bytes": (c_sz, [ctypes.POINTER(MgsVolumeArgs)]),
+    "mgs_volume_resample_pad_forward": (ctypes.c_int, [ctypes.POINTER(MgsVolumeArgs), c_fp, c_fp]),
+    "mgs_volume_resample_pad_backward": (ctypes.c_int, [ctypes.POINTER(MgsVolumeArgs), c_fp, ctypes.POINTER(c_fp), c_fp, c_sz, c_fp]),
     "mgs_forward_stats": (ctypes.c_int, [ctypes.POINTER(MgsRasterArgs), c_i32, ctypes.POINTER(ctypes.c_int64),
                                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), c_fp]),
     "mgs_debug_geom_layout": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(c_sz)] * 4),

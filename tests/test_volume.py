@@ -1,0 +1,387 @@
+"""The fused trilinear upsample + channel concatenation + replicate pad (manigaussian_amd/volume.py, csrc/mgs_volume.hip) and the
+Conv3DBlock / Conv3DUpsampleBlock drop-ins, against torch's own composition and ManiGaussian's own classes
+(helpers/network_utils.py:129-171, 374-391).
+
+The yardstick is the reference's own fp32 rounding error (tests/volume_cases.py): the truth is the plain torch composition in
+float64, ref_err the same composition's float32 deviation from it over max|truth|, and ours must satisfy
+  |ours - truth| <= 16 x max(ref_err, 2^-23) x max|truth|
+for the output and every source gradient, and be bit-equal where ref_err == 0 (the scale == 1 forward is a copy).  The smallest
+logic error -- one tap off, one border row counted once too few -- is of order 1e-1.
+At the production shapes no CPU truth exists: the truth is torch's composition in float64 on the GPU, the yardstick its float32
+run on the same GPU.  The module fixtures also bound ours by twice what torch's own layers give on the same device, because the
+convolution between the fused pieces is MIOpen's.
+"""
+import ctypes
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import volume_cases as vc
+
+gpu = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# name: (the sources' shapes, scale, pad)
+PRODUCTION = {"up0": (((1, 128, 20, 20, 20),), 5, 2),
+              "final": (((1, 128, 100, 100, 100), (1, 128, 100, 100, 100)), 1, 1),
+              "long_odd": (((1, 3, 101, 99, 103),), 1, 2)}
+
+
+# ---- CPU -----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", list(vc.CASES))
+def test_the_axis_matrices_reproduce_the_composition(case):
+    """Pins axis_weights(), the formula the kernels implement, against F.interpolate + F.pad in float64: forward and gradient."""
+    _, s, p = vc.CASES[case]
+    t = vc.truth(case)
+    leaves = [x.double().clone().requires_grad_(True) for x in t["sources"]]
+    out = vc.restatement(leaves, s, p)
+    out.backward(t["upstream"].double())
+    assert out.shape == t["out64"].shape
+    assert vc.rel_err(out.detach(), t["out64"]) <= 1e-12, case
+    for k, (leaf, want) in enumerate(zip(leaves, t["grads64"])):
+        assert vc.rel_err(leaf.grad, want) <= 1e-12, (case, k)
+    for n in set(t["sources"][0].shape[2:]):
+        A = vc.axis_weights(n, s, p)
+        assert torch.equal(A.sum(1), torch.ones(s * n + 2 * p, dtype=A.dtype)) or (A.sum(1) - 1).abs().max() <= 1e-15
+        assert (A.to_sparse().coalesce().indices()[0].bincount(minlength=A.shape[0]) <= 2).all(), "at most two taps per output"
+        # float32 arithmetic for 1 / s and lambda (the kernels') moves a weight by rounding only
+        assert (vc.axis_weights(n, s, p, torch.float32).double() - A).abs().max().item() <= 2.0 ** -20
+
+
+def test_the_cases_yardsticks_stay_under_the_ceiling_and_copies_are_exact():
+    for case, (_, s, _) in vc.CASES.items():
+        e = vc.truth(case)["ref_err"]
+        assert max([e["out"]] + e["grads"]) <= vc.REF_ERR_CEILING, (case, e)
+        if s == 1:
+            assert e["out"] == 0.0, case
+    assert vc.truth("identity")["ref_err"]["grads"] == [0.0]
+    view = vc.make_sources("cat_pad1")[1]
+    assert view.shape[1] == 3 and view._base.shape[1] == 5 and view.storage_offset() == 3 * 4 * 5, "channels 1..3 of five, a view"
+
+
+@pytest.mark.skipif(not vc.have_reference(), reason="no copy of the reference on this machine")
+def test_module_fixtures_match_the_reference():
+    """The generator's computation, re-run.  Inputs and parameters bit for bit; the float64 truth to 1e-12 of its magnitude (the
+    order of a CPU's sums may follow its thread count); the yardsticks, maxima of float32 rounding errors, within a factor of 4."""
+    for name in vc.MODULES:
+        f, now = vc.load_module_fixture(name), vc.reference_module_case(name)
+        assert set(now) == set(f), name
+        for k, v in now.items():
+            if k.startswith("ref_err."):
+                e, c = float(v), f[k]
+                assert (e == 0 and c == 0) or 0.25 * c <= e <= 4 * c, (name, k, e, c)
+                assert e <= vc.REF_ERR_CEILING, (name, k, e)
+            elif v.dtype == np.float64:
+                assert vc.rel_err(torch.from_numpy(v), f[k]) <= 1e-12, (name, k)
+            else:
+                assert np.array_equal(v, f[k].numpy()), (name, k)
+
+
+def test_module_fixtures_are_small():
+    for name in vc.MODULES:
+        assert os.path.getsize(vc.module_fixture_path(name)) <= 1_000_000, name
+        with np.load(vc.module_fixture_path(name), allow_pickle=False) as z:
+            assert all(z[k].dtype.kind in "fi" for k in z.files), name
+            assert max(float(z[k]) for k in z.files if k.startswith("ref_err.")) <= vc.REF_ERR_CEILING, name
+            assert sorted(k[2:] for k in z.files if k.startswith("p.")) == vc.STATE_KEYS[name], name
+
+
+def check_module(name, errors, tag, torch_errors=None):
+    """errors: vc.module_errors of ours; torch_errors: those of torch's own layers on the same device (the GPU tests)."""
+    for k, (err, ref_err) in errors.items():
+        allowed = vc.bound(ref_err)
+        if torch_errors is not None:
+            allowed = max(allowed, 2.0 * torch_errors[k][0])
+        print(f"{name} {tag} {k}: err {err:.3e}, ref_err {ref_err:.3e}"
+              + (f", torch on this device {torch_errors[k][0]:.3e}" if torch_errors is not None else "") + f", bound {allowed:.3e}")
+        assert err <= allowed, (name, tag, k, err, allowed)
+
+
+@pytest.mark.parametrize("name", list(vc.MODULES))
+def test_the_drop_ins_reproduce_every_fixture_on_the_cpu(name):
+    import manigaussian_amd
+    f = vc.load_module_fixture(name)
+    m = vc.fixture_module(manigaussian_amd, name)
+    assert sorted(m.state_dict()) == vc.STATE_KEYS[name]
+    out, dx, dp = vc.run_module(m, f["x"], f["g"], torch.float32)
+    assert out.shape == f["out64"].shape
+    check_module(name, vc.module_errors(f, out, dx, dp), "cpu")
+    if name in vc.SPLIT:
+        out, dx, dp = vc.run_module(m, f["x"], f["g"], torch.float32, split=vc.SPLIT[name])
+        check_module(name, vc.module_errors(f, out, dx, dp), "cpu, as a list")
+
+
+def test_the_drop_ins_keep_the_references_interface():
+    from manigaussian_amd import Conv3DBlock, Conv3DUpsampleBlock
+    b = Conv3DBlock(3, 4)
+    assert b.conv3d.kernel_size == (3, 3, 3) and b.conv3d.padding == (1, 1, 1) and b.conv3d.padding_mode == "replicate"
+    assert b.activation is None and b.norm is None and b.out_channels == 4 and b.fused_pad() == 1
+    assert torch.equal(b.conv3d.bias, torch.zeros(4))
+    assert Conv3DBlock(3, 4, 5, 5, activation="lrelu").activation.negative_slope == 0.02
+    assert Conv3DBlock(3, 4, 5, padding=0).fused_pad() == 0
+    with pytest.raises(NotImplementedError, match="Norm not implemented"):
+        Conv3DBlock(3, 4, norm="batch")
+    with pytest.raises(ValueError):
+        Conv3DBlock(3, 4, activation="gelu")
+    # another padding mode is nn.Conv3d's own business
+    z = Conv3DBlock(3, 4, padding_mode="zeros", activation="relu")
+    x = torch.randn(1, 3, 4, 4, 4, generator=torch.Generator().manual_seed(1))
+    assert z.fused_pad() is None and torch.equal(z(x), torch.relu(z.conv3d(x))) and torch.equal(z([x[:, :1], x[:, 1:]]), z(x))
+    up = Conv3DUpsampleBlock(3, 4, 2, kernel_sizes=3, activation="lrelu")
+    assert isinstance(up.conv_up[1], torch.nn.Upsample) and len(list(up.conv_up[1].parameters())) == 0
+    assert len(Conv3DUpsampleBlock(3, 4, 1).conv_up) == 2
+
+
+@pytest.mark.skipif(not vc.have_reference(), reason="no copy of the reference on this machine")
+@pytest.mark.parametrize("name", list(vc.MODULES))
+def test_a_reference_state_dict_loads_strict_both_ways_and_the_inits_agree(name):
+    import manigaussian_amd
+    ref = vc.load_reference()
+    cls, kw, _ = vc.MODULES[name]
+    with torch.random.fork_rng():
+        torch.manual_seed(77)
+        theirs = getattr(ref, cls)(**kw)
+        torch.manual_seed(77)
+        ours = getattr(manigaussian_amd, cls)(**kw)
+    assert sorted(theirs.state_dict()) == sorted(ours.state_dict()) == vc.STATE_KEYS[name]
+    for k, v in theirs.state_dict().items():
+        assert vc.same_bits(v, ours.state_dict()[k]), (name, k, "the same seed gives the reference's initial parameters")
+    mine = vc.fixture_module(manigaussian_amd, name)
+    theirs.load_state_dict(mine.state_dict(), strict=True)
+    ours.load_state_dict(theirs.state_dict(), strict=True)
+    f = vc.load_module_fixture(name)
+    assert all(torch.equal(ours.state_dict()[k], f["p." + k]) for k in vc.STATE_KEYS[name])
+
+
+def test_resample_pad_on_cpu_tensors_is_the_composition_and_refuses_bad_input():
+    from manigaussian_amd import resample_pad
+    for case, (_, s, p) in vc.CASES.items():
+        t = vc.truth(case)
+        assert torch.equal(resample_pad(t["sources"], s, p), vc.compose(t["sources"], s, p)), case
+    x = torch.zeros(1, 2, 3, 4, 5)
+    assert resample_pad(x, 2, 1).shape == (1, 2, 8, 10, 12) and resample_pad((x, x), pad=2).shape == (1, 4, 7, 8, 9)
+    for bad in (dict(scale=0), dict(scale=9), dict(pad=-1), dict(pad=9)):
+        with pytest.raises(ValueError, match="scale ="):
+            resample_pad(x, **bad)
+    with pytest.raises(ValueError, match="sources"):
+        resample_pad([x] * 5)
+    with pytest.raises(ValueError, match="sources"):
+        resample_pad([])
+    with pytest.raises(ValueError, match="differ"):
+        resample_pad([x, torch.zeros(1, 2, 3, 4, 6)])
+    with pytest.raises(ValueError, match="differ"):
+        resample_pad([x, torch.zeros(2, 2, 3, 4, 5)])
+    with pytest.raises(ValueError, match="float32"):
+        resample_pad(x.double())
+    with pytest.raises(ValueError, match="float32"):
+        resample_pad(torch.zeros(2, 3, 4, 5))
+    with pytest.raises(ValueError, match="empty"):
+        resample_pad(torch.zeros(1, 0, 3, 4, 5))
+
+
+def _volume_args(B=2, D=4, H=5, W=6, scale=5, pad=2, C=(3,), src=0x10000, strides=None):
+    from manigaussian_amd import _lib
+    a = _lib.MgsVolumeArgs()
+    a.B, a.D, a.H, a.W, a.scale, a.pad, a.nsrc = B, D, H, W, scale, pad, len(C)
+    for k, c in enumerate(C[:_lib.VOLUME_MAX_SOURCES]):
+        a.C[k], a.src[k] = c, src
+        a.stride_b[k], a.stride_c[k] = strides if strides else (c * D * H * W, D * H * W)
+    return a
+
+
+def test_the_library_refuses_bad_arguments_before_any_launch():
+    """With fake pointers: a call that got as far as a launch would not come back with MGS_ERR_INVALID_ARG."""
+    from manigaussian_amd import _lib
+    L = _lib.lib()
+    fake, INV = 0x10000, _lib.MGS_ERR_INVALID_ARG
+    big = 1 << 40
+
+    def fwd(a, out=fake):
+        return L.mgs_volume_resample_pad_forward(ctypes.byref(a) if a is not None else None, out, None)
+
+    def bwd(a, g_out=fake, g_src=(fake,) * 4, ws=fake, ws_bytes=big):
+        pointers = (_lib.c_fp * 4)(*g_src) if g_src is not None else None
+        return L.mgs_volume_resample_pad_backward(ctypes.byref(a) if a is not None else None, g_out, pointers, ws, ws_bytes, None)
+
+    shape_cases = ((dict(scale=0), "scale = 0"), (dict(scale=9), "scale = 9"), (dict(pad=-1), "pad = -1"), (dict(pad=9), "pad = 9"),
+                   (dict(C=(1, 1, 1, 1, 1)), "nsrc = 5"), (dict(C=()), "nsrc = 0"), (dict(C=(3, 0)), "C[1] = 0"),
+                   (dict(C=(-2,)), "C[0] = -2"), (dict(B=-1), "B = -1"), (dict(D=0), "D = 0"), (dict(H=-3), "H = -3"),
+                   (dict(W=0), "W = 0"),
+                   (dict(B=1, C=(2,), D=1024, H=1024, W=1024, scale=1, pad=0), "2^31 - 1"),      # a source of 2^31 elements
+                   (dict(B=1, C=(128,), D=60, H=60, W=60, scale=5, pad=2), "2^31 - 1"),          # only the padded output is too large
+                   (dict(B=1, C=(1,), D=1, H=1, W=(1 << 31) - 1, scale=1, pad=1), "2^31 - 1"))   # 2^31 - 1 fits, its pad does not
+    for kw, word in shape_cases:
+        a = _volume_args(**kw)
+        for call in (fwd, bwd):
+            assert call(a) == INV, (call.__name__, kw)
+            assert word in _lib.last_error(), (call.__name__, kw, _lib.last_error())
+        assert L.mgs_volume_workspace_bytes(ctypes.byref(a)) == 0, kw
+    ok = _volume_args()
+    for call in (fwd, bwd):
+        assert call(None) == INV and "NULL" in _lib.last_error()
+    assert fwd(ok, out=None) == INV and "NULL" in _lib.last_error()
+    assert fwd(ok, out=fake + 4) == INV and "16-byte aligned" in _lib.last_error()
+    assert fwd(_volume_args(src=None)) == INV and "src[0]" in _lib.last_error()
+    assert fwd(_volume_args(src=fake + 2)) == INV and "4-byte aligned" in _lib.last_error()
+    second = _volume_args(C=(2, 3), scale=1, pad=1)
+    second.src[1] = None
+    assert fwd(second) == INV and "src[1]" in _lib.last_error()
+    assert bwd(ok, g_out=None) == INV and "NULL" in _lib.last_error()
+    assert bwd(ok, g_src=None) == INV and "NULL" in _lib.last_error()
+    assert bwd(ok, g_src=(None, fake, fake, fake)) == INV and "g_src[0]" in _lib.last_error()
+    assert bwd(ok, g_src=(fake + 8, fake, fake, fake)) == INV and "16-byte aligned" in _lib.last_error()
+    assert bwd(_volume_args(C=(2, 3)), g_src=(fake, None, fake, fake)) == INV and "g_src[1]" in _lib.last_error()
+    assert bwd(ok, ws=None) == INV and "workspace" in _lib.last_error()
+    need = L.mgs_volume_workspace_bytes(ctypes.byref(ok))
+    assert bwd(ok, ws_bytes=need - 1) == INV and "needed" in _lib.last_error()
+    assert bwd(ok, ws_bytes=0) == INV and "needed" in _lib.last_error()
+    # an empty batch is no error and no launch (there is no device on this machine to launch on)
+    empty = _volume_args(B=0)
+    assert fwd(empty) == _lib.MGS_OK and bwd(empty, ws_bytes=L.mgs_volume_workspace_bytes(ctypes.byref(empty))) == _lib.MGS_OK
+    assert fwd(_volume_args(B=0, scale=9)) == INV
+
+
+def test_the_workspace_size_is_positive_and_monotone():
+    from manigaussian_amd import _lib
+    L = _lib.lib()
+
+    def size(**kw):
+        return L.mgs_volume_workspace_bytes(ctypes.byref(_volume_args(**kw)))
+
+    up0 = size(B=1, C=(128,), D=20, H=20, W=20, scale=5, pad=2)
+    assert 128 * 104 * 400 * 4 <= up0 <= 128 * 104 * 400 * 4 + 512 and up0 % 256 == 0, "x and y reduced per padded z-plane: 21 MB"
+    for kw in (dict(B=1, C=(1,), D=1, H=1, W=1, scale=1, pad=0), dict(B=1, C=(128, 128), D=100, H=100, W=100, scale=1, pad=1),
+               dict(B=0), dict(B=1, C=(1,), D=1, H=1, W=1, scale=8, pad=8)):
+        assert size(**kw) > 0, kw
+    base = dict(B=2, C=(3, 2), D=4, H=5, W=6, scale=2, pad=1)
+    for key, larger in (("B", 3), ("C", (3, 3)), ("C", (3, 2, 1)), ("D", 5), ("H", 6), ("W", 7), ("scale", 3), ("pad", 2)):
+        assert size(**dict(base, **{key: larger})) >= size(**base) > 0, key
+    sizes = [size(B=1, C=(c,), D=20, H=20, W=20, scale=5, pad=2) for c in (1, 2, 64, 128, 256)]
+    assert all(a < b for a, b in zip(sizes, sizes[1:]))
+    assert size(B=1, C=(128, 128), D=100, H=100, W=100, scale=1, pad=1) <= 4096, "the copy's backward needs no intermediate"
+
+
+# ---- GPU -----------------------------------------------------------------------------------------------------------------------
+def dev():
+    return torch.device("cuda:0")
+
+
+def run(sources, upstream, s, p):
+    """(out, [source gradients]) of the fused op on the device; the sources are used as they are (views stay views)."""
+    from manigaussian_amd import resample_pad
+    leaves = [t.detach().requires_grad_(True) for t in sources]
+    out = resample_pad(leaves, s, p)
+    grads = torch.autograd.grad(out, leaves, upstream)
+    return out.detach(), list(grads)
+
+
+def check(tag, got, truth, ref_err):
+    err, allowed = vc.rel_err(got.cpu(), truth.cpu()), vc.bound(ref_err)
+    print(f"{tag}: err {err:.3e}, ref_err {ref_err:.3e}, bound {allowed:.3e}")
+    if ref_err == 0:
+        assert vc.same_bits(got.cpu(), truth.float().cpu()), (tag, "the reference is exact here: bit-equal")
+    assert err <= allowed, (tag, err, allowed)
+
+
+@gpu
+@pytest.mark.parametrize("case", list(vc.CASES))
+def test_every_case_forward_and_gradients(case):
+    _, s, p = vc.CASES[case]
+    t = vc.truth(case)
+    sources = vc.make_sources(case, dev())
+    out, grads = run(sources, t["upstream"].to(dev()), s, p)
+    assert out.shape == t["out64"].shape and out.is_contiguous()
+    check(f"{case} out", out, t["out64"], t["ref_err"]["out"])
+    for k, (g, want, e) in enumerate(zip(grads, t["grads64"], t["ref_err"]["grads"])):
+        assert g.shape == want.shape and g.is_contiguous()
+        check(f"{case} grad {k}", g, want, e)
+
+
+@gpu
+def test_a_channel_slice_is_read_in_place():
+    from manigaussian_amd.volume import _in_place
+    _, s, p = vc.CASES["cat_pad1"]
+    views = vc.make_sources("cat_pad1", dev())
+    assert views[1]._base is not None and _in_place(views[1]) is views[1], "no copy is made of the slice"
+    up = vc.make_upstream("cat_pad1", dev())
+    a = run(views, up, s, p)
+    b = run([v.contiguous() for v in views], up, s, p)
+    assert vc.same_bits(a[0], b[0]) and all(vc.same_bits(x, y) for x, y in zip(a[1], b[1]))
+    # ... and with a batch of two, where the slice's batch stride is the wider tensor's
+    _, s2, p2 = vc.CASES["cat3_up2"]
+    whole, up2 = vc.make_sources("cat3_up2", dev()), vc.make_upstream("cat3_up2", dev())
+    wider = torch.full((2, 4, 2, 3, 4), float("nan"), device=dev())
+    wider[:, 1:3] = whole[2]
+    sliced = wider[:, 1:3]
+    assert not sliced.is_contiguous() and _in_place(sliced) is sliced
+    d, e = run(whole, up2, s2, p2), run(whole[:2] + [sliced], up2, s2, p2)
+    assert vc.same_bits(d[0], e[0]) and all(vc.same_bits(x, y) for x, y in zip(d[1], e[1]))
+    # a layout the kernels do not read (channels last in memory) is copied, not misread
+    odd = views[0].permute(0, 2, 3, 4, 1).contiguous().permute(0, 4, 1, 2, 3)
+    c = run([odd, views[1]], up, s, p)
+    assert vc.same_bits(a[0], c[0]) and all(vc.same_bits(x, y) for x, y in zip(a[1], c[1]))
+
+
+def production_inputs(name):
+    shapes, s, p = PRODUCTION[name]
+    gen = torch.Generator(device=dev()).manual_seed(6000 + list(PRODUCTION).index(name))
+    sources = [torch.randn(*sh, device=dev(), generator=gen) for sh in shapes]
+    B, _, D, H, W = shapes[0]
+    up = torch.randn(B, sum(sh[1] for sh in shapes), s * D + 2 * p, s * H + 2 * p, s * W + 2 * p, device=dev(), generator=gen)
+    return sources, up, s, p
+
+
+@gpu
+@pytest.mark.parametrize("case", ["up5", "cat3_up2", "up0"])
+def test_two_runs_are_bit_identical(case):
+    if case in PRODUCTION:
+        sources, up, s, p = production_inputs(case)
+    else:
+        sources, up, (_, s, p) = vc.make_sources(case, dev()), vc.make_upstream(case, dev()), vc.CASES[case]
+    a, b = run(sources, up, s, p), run(sources, up, s, p)
+    assert torch.equal(a[0], b[0]) and all(torch.equal(x, y) for x, y in zip(a[1], b[1])), case
+
+
+@gpu
+@pytest.mark.parametrize("name", list(PRODUCTION))
+def test_production_shapes_against_float64_on_the_device(name):
+    sources, up, s, p = production_inputs(name)
+    out, grads = run(sources, up, s, p)
+    if s == 1:
+        assert torch.equal(out, F.pad(torch.cat(sources, 1), (p,) * 6, mode="replicate")), (name, "the copy is bit-equal")
+    out32, g32 = vc.compose_with_grads(sources, up, s, p, torch.float32)
+    out64, g64 = vc.compose_with_grads(sources, up, s, p, torch.float64)
+    pairs = [("out", out, out32, out64)] + [(f"grad {k}", g, a, b) for k, (g, a, b) in enumerate(zip(grads, g32, g64))]
+    del out32, g32
+    for what, ours, ref32, ref64 in pairs:
+        mag = ref64.abs().max().item()
+        ref_err = (ref32.double() - ref64).abs().max().item() / mag
+        err = (ours.double() - ref64).abs().max().item() / mag
+        print(f"{name} {what}: err {err:.3e}, torch float32 on this device {ref_err:.3e}, bound {vc.bound(ref_err):.3e}")
+        assert ours.shape == ref64.shape and err <= vc.bound(ref_err), (name, what, err, ref_err)
+
+
+@gpu
+@pytest.mark.parametrize("name", list(vc.MODULES))
+def test_module_fixtures_on_the_device(name):
+    """Ours against the fixture's truth, beside torch's own layers with the same parameters on the same device."""
+    import manigaussian_amd
+    f = vc.load_module_fixture(name)
+    theirs = vc.module_errors(f, *vc.run_module(vc.fixture_module(vc.plain, name), f["x"], f["g"], torch.float32, dev()))
+    m = vc.fixture_module(manigaussian_amd, name)
+    check_module(name, vc.module_errors(f, *vc.run_module(m, f["x"], f["g"], torch.float32, dev())), "device", theirs)
+    if name in vc.SPLIT:
+        ours = vc.module_errors(f, *vc.run_module(m, f["x"], f["g"], torch.float32, dev(), split=vc.SPLIT[name]))
+        check_module(name, ours, "device, as a list", theirs)
+
+
+@gpu
+def test_forward_and_backward_captured_into_a_hip_graph():
+    """In a child process: stream capture is process-wide state (tests/tools/volume_graph_capture_check.py)."""
+    tool = os.path.join(ROOT, "tests", "tools", "volume_graph_capture_check.py")
+    r = subprocess.run(["timeout", "-k", "10", "150", sys.executable, tool], capture_output=True, text=True, timeout=170)
+    assert r.returncode == 0 and "GRAPH_OK" in r.stdout, f"exit {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"

@@ -10,7 +10,8 @@ import weakref
 
 import torch
 
-from . import _lib, _state
+from . import _lib, _ops, _state
+from ._ops import on_device as _on_device, ptr as _ptr, stream as _stream
 
 _F32 = torch.float32
 
@@ -20,10 +21,6 @@ def _padded_F(F: int) -> int:
         if F <= s:
             return s
     raise RuntimeError(f"language feature width {F} > {_lib.SUPPORTED_F[-1]} is not supported")
-
-
-def _ptr(t):
-    return None if (t is None or t.numel() == 0) else t.data_ptr()
 
 
 def _f32c(t, name, dev):
@@ -49,26 +46,6 @@ def _aligned16(t):
 def _sh_coeffs(sh, S):
     """SH coefficients per Gaussian: sh is [P,M,3], or [S,P,M,3] in a batch of S Gaussian sets (S > 0)."""
     return int(sh.size(2 if S else 1)) if sh.numel() != 0 else 0
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device()))
-
-
-class _on_device:
-    """`with torch.cuda.device(dev)` only when dev is not already current (the context manager costs ~10 us)."""
-
-    def __init__(self, dev):
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        self.ctx = None if idx == torch.cuda.current_device() else torch.cuda.device(idx)
-
-    def __enter__(self):
-        if self.ctx is not None:
-            self.ctx.__enter__()
-
-    def __exit__(self, *a):
-        if self.ctx is not None:
-            self.ctx.__exit__(*a)
 
 
 def _fill_args(a, *, P, D, M, F, W, H, tanfovx, tanfovy, scale_modifier, prefiltered, debug, include_feature,
@@ -685,17 +662,14 @@ def _backward(background, means3D, radii, colors, language_feature, scales, rota
 
 def mark_visible(means3D, viewmatrix, projmatrix):
     """markVisible (RAST/rasterize_points.cu:227-246): bool [P], True where view-space z > 0.2."""
-    L = _lib.lib()
     if not means3D.is_cuda:
         raise RuntimeError("mark_visible needs tensors on a HIP device; there is no CPU path")
     dev = means3D.device
     P = int(means3D.size(0))
     present = torch.zeros((P,), dtype=torch.bool, device=dev)
     if P != 0:
-        with torch.cuda.device(dev):
-            m = _f32c(means3D, "means3D", dev)
-            v = _f32c(viewmatrix, "viewmatrix", dev)
-            p = _f32c(projmatrix, "projmatrix", dev)
-            _lib.check(L.mgs_mark_visible(P, m.data_ptr(), v.data_ptr(), p.data_ptr(), present.data_ptr(),
-                                          _stream(dev)), "mark_visible")
+        m = _f32c(means3D, "means3D", dev)
+        v = _f32c(viewmatrix, "viewmatrix", dev)
+        p = _f32c(projmatrix, "projmatrix", dev)
+        _ops.call("mgs_mark_visible", dev, P, m.data_ptr(), v.data_ptr(), p.data_ptr(), present.data_ptr())
     return present

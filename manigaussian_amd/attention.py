@@ -19,24 +19,9 @@ import ctypes
 import torch
 from torch import nn
 
-from . import _lib
+from . import _lib, _ops
 
 DIM_HEAD = 64  # the only head dimension the library compiles
-
-_WORKSPACES = {}  # (device index, bytes) -> uint8 tensor (D_i of the backward; written before it is read in every call)
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _workspace(dev, B, H, Nq, Nk):
-    n = _lib.lib().mgs_attention_workspace_bytes(B, H, Nq, Nk)
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), n)
-    ws = _WORKSPACES.get(key)
-    if ws is None:
-        ws = _WORKSPACES[key] = torch.empty(n, dtype=torch.uint8, device=dev)
-    return ws
 
 
 def _copy(t):
@@ -88,9 +73,7 @@ class _FusedAttention(torch.autograd.Function):
         a = _lib.MgsAttentionArgs()
         _fill(a, q, k, v, heads, mask, dropout_p, rng)
         a.out_stride_b, a.out_stride_n = out.stride(0), out.stride(1)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().mgs_attention_forward(ctypes.byref(a), out.data_ptr(), lse.data_ptr(), _stream(dev)),
-                       "attention_forward")
+        _ops.call("mgs_attention_forward", dev, ctypes.byref(a), out.data_ptr(), lse.data_ptr())
         ctx.save_for_backward(q, kv if packed else k, v if not packed else None, mask, rng, out, lse)
         ctx.packed, ctx.heads, ctx.dropout_p = packed, heads, dropout_p
         return out
@@ -105,17 +88,16 @@ class _FusedAttention(torch.autograd.Function):
         Nk = k.size(1)
         dq = torch.empty(B, Nq, HD, dtype=torch.float32, device=dev)
         dkv = torch.empty(B, Nk, 2 * HD, dtype=torch.float32, device=dev)
-        ws = _workspace(dev, B, ctx.heads, Nq, Nk)
+        # D_i of the backward: written before it is read in every call
+        ws = _ops.workspace(dev, _lib.lib().mgs_attention_workspace_bytes(B, ctx.heads, Nq, Nk))
         a = _lib.MgsAttentionArgs()
         _fill(a, q, k, v, ctx.heads, mask, ctx.dropout_p, rng)
         a.out_stride_b, a.out_stride_n = out.stride(0), out.stride(1)
         a.dout_stride_b, a.dout_stride_n = d_out.stride(0), d_out.stride(1)
         a.dq_stride_b, a.dq_stride_n = dq.stride(0), dq.stride(1)
         a.dkv_stride_b, a.dkv_stride_n = dkv.stride(0), dkv.stride(1)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().mgs_attention_backward(ctypes.byref(a), out.data_ptr(), lse.data_ptr(), d_out.data_ptr(),
-                                                         dq.data_ptr(), dkv.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
-                       "attention_backward")
+        _ops.call("mgs_attention_backward", dev, ctypes.byref(a), out.data_ptr(), lse.data_ptr(), d_out.data_ptr(),
+                  dq.data_ptr(), dkv.data_ptr(), ws.data_ptr(), ws.numel())
         if ctx.packed:
             return dq, dkv, None, None, None, None, None, None
         dk, dv = dkv.chunk(2, dim=-1)
@@ -178,9 +160,7 @@ def dropout_keep_mask(B, heads, Nq, Nk, dropout_p, rng_state):
     a = _lib.MgsAttentionArgs()
     a.B, a.H, a.Nq, a.Nk, a.D, a.dropout_p = B, heads, Nq, Nk, DIM_HEAD, float(dropout_p)
     a.rng_state = rng_state.data_ptr()
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mgs_attention_dropout_mask(ctypes.byref(a), keep.data_ptr(), _stream(dev)),
-                   "attention_dropout_mask")
+    _ops.call("mgs_attention_dropout_mask", dev, ctypes.byref(a), keep.data_ptr())
     return keep
 
 

@@ -25,7 +25,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _ops
 
 
 def parse_camera_file(file_path):
@@ -77,7 +77,6 @@ def get_novel_calib(data, W, H, znear=0.1, zfar=4.0, trans=(0.0, 0.0, 0.0), scal
     """Drop-in for NeuralRenderer.get_novel_calib (neural_rendering.py:205-248): data['intr'] [bs,3,3], data['extr']
     [bs,4,4] (cam2world) on a HIP device -> the same dict (FovX, FovY, width, height, world_view_transform,
     full_proj_transform, camera_center), computed by one kernel without leaving the device, plus 'tanfov' [bs,2]."""
-    L = _lib.lib()
     intr, extr = data["intr"], data["extr"]
     if not intr.is_cuda:
         raise RuntimeError("get_novel_calib needs tensors on a HIP device (novel_calib_host is the host-side routine)")
@@ -88,12 +87,9 @@ def get_novel_calib(data, W, H, znear=0.1, zfar=4.0, trans=(0.0, 0.0, 0.0), scal
     o = dict(dtype=torch.float32, device=dev)
     wvt, fpt = torch.empty((bs, 4, 4), **o), torch.empty((bs, 4, 4), **o)
     centre, fov, tanfov = torch.empty((bs, 3), **o), torch.empty((bs, 2), **o), torch.empty((bs, 2), **o)
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(L.mgs_novel_calib(bs, e.data_ptr(), k.data_ptr(), int(W), int(H), float(znear), float(zfar),
-                                     float(trans[0]), float(trans[1]), float(trans[2]), float(scale), wvt.data_ptr(),
-                                     fpt.data_ptr(), centre.data_ptr(), fov.data_ptr(), tanfov.data_ptr(), None, stream),
-                   "novel_calib")
+    _ops.call("mgs_novel_calib", dev, bs, e.data_ptr(), k.data_ptr(), int(W), int(H), float(znear), float(zfar),
+              float(trans[0]), float(trans[1]), float(trans[2]), float(scale), wvt.data_ptr(),
+              fpt.data_ptr(), centre.data_ptr(), fov.data_ptr(), tanfov.data_ptr(), None)
     return {"FovX": fov[:, 0], "FovY": fov[:, 1], "width": torch.full((bs,), int(W), device=dev),
             "height": torch.full((bs,), int(H), device=dev), "world_view_transform": wvt, "full_proj_transform": fpt,
             "camera_center": centre, "tanfov": tanfov}

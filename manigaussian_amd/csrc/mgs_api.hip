@@ -22,6 +22,20 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+int launch_done(const char* fn) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { set_error("%s: %s", fn, hipGetErrorString(e)); return MGS_ERR_HIP; }
+  return MGS_OK;
+}
+
+bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
+
+int workspace_short(const char* fn, size_t have, size_t need) {
+  if (have >= need) return MGS_OK;
+  set_error("%s: workspace of %zu bytes, %zu needed", fn, have, need);
+  return MGS_ERR_WORKSPACE;
+}
+
 // Nonces of the preprocess's table hand-shake: a process-wide counter under a per-process random word, never 0.  Not
 // option state and not device state: two calls never share a value, that is all.
 unsigned long long next_nonce() {

@@ -377,7 +377,6 @@ __global__ void __launch_bounds__(256) attn_mask_kernel(AttnK a, uint8_t* __rest
 }
 
 // =====================================================================================================================
-static bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 static bool bad_stride(int64_t sn, int64_t sb, int64_t row) { return sn < row || (sn & 3) != 0 || (sb & 3) != 0 || sb < 0; }
 
 static int attn_check(const char* fn, const MgsAttentionArgs* a) {
@@ -401,7 +400,7 @@ static int attn_check(const char* fn, const MgsAttentionArgs* a) {
 
 static int attn_check_qkv(const char* fn, const MgsAttentionArgs* a) {
   if (!a->q || !a->k || !a->v) { set_error("%s: NULL q, k or v", fn); return MGS_ERR_INVALID_ARG; }
-  if (misaligned(a->q) || misaligned(a->k) || misaligned(a->v)) {
+  if (misaligned16(a->q) || misaligned16(a->k) || misaligned16(a->v)) {
     set_error("%s: q, k and v must be 16-byte aligned", fn);
     return MGS_ERR_INVALID_ARG;
   }
@@ -434,12 +433,6 @@ static AttnK attn_args(const MgsAttentionArgs* a) {
   k.scale = 0.125f;  // 64 ** -0.5
   k.inv_nk = 1.f / (float)a->Nk;
   return k;
-}
-
-static int attn_done(const char* fn) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("%s: %s", fn, hipGetErrorString(e)); return MGS_ERR_HIP; }
-  return MGS_OK;
 }
 
 // rows = queries (forward, dQ) or keys (dK/dV) each (batch, head) splits among workgroups
@@ -476,7 +469,7 @@ int mgs_attention_forward(const MgsAttentionArgs* a, float* out, float* lse, mgs
   int rc = attn_check(fn, a);
   if (rc == MGS_OK) rc = attn_check_qkv(fn, a);
   if (rc != MGS_OK) return rc;
-  if (!out || !lse || misaligned(out) || bad_stride(a->out_stride_n, a->out_stride_b, (int64_t)a->H * ATT_D)) {
+  if (!out || !lse || misaligned16(out) || bad_stride(a->out_stride_n, a->out_stride_b, (int64_t)a->H * ATT_D)) {
     set_error("%s: out and lse must be given, out 16-byte aligned with a row stride (%lld) that is a multiple of 4 and at least "
               "the row", fn, (long long)a->out_stride_n);
     return MGS_ERR_INVALID_ARG;
@@ -486,7 +479,7 @@ int mgs_attention_forward(const MgsAttentionArgs* a, float* out, float* lse, mgs
   hipStream_t s = (hipStream_t)stream;
   const bool drop = a->dropout_p > 0.f;
   ATT_LAUNCH(attn_fwd_kernel, a->Nq, drop, s, k);
-  return attn_done(fn);
+  return launch_done(fn);
 }
 
 int mgs_attention_backward(const MgsAttentionArgs* a, const float* out, const float* lse, const float* d_out, float* dq,
@@ -497,7 +490,7 @@ int mgs_attention_backward(const MgsAttentionArgs* a, const float* out, const fl
   if (rc != MGS_OK) return rc;
   const int64_t row = (int64_t)a->H * ATT_D;
   if (!out || !lse || !d_out || !dq || !dkv || !workspace) { set_error("%s: NULL pointer", fn); return MGS_ERR_INVALID_ARG; }
-  if (misaligned(out) || misaligned(d_out) || misaligned(dq) || misaligned(dkv) || misaligned(workspace)) {
+  if (misaligned16(out) || misaligned16(d_out) || misaligned16(dq) || misaligned16(dkv) || misaligned16(workspace)) {
     set_error("%s: out, d_out, dq, dkv and the workspace must be 16-byte aligned", fn);
     return MGS_ERR_INVALID_ARG;
   }
@@ -509,10 +502,7 @@ int mgs_attention_backward(const MgsAttentionArgs* a, const float* out, const fl
     return MGS_ERR_INVALID_ARG;
   }
   const size_t need = mgs_attention_workspace_bytes(a->B, a->H, a->Nq, a->Nk);
-  if (workspace_bytes < need) {
-    set_error("%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, need);
-    return MGS_ERR_WORKSPACE;
-  }
+  if (int rc = workspace_short(fn, workspace_bytes, need)) return rc;
   AttnK k = attn_args(a);
   k.o_in = out; k.lse = const_cast<float*>(lse); k.d_out = d_out; k.dq = dq; k.dkv = dkv;
   k.delta = reinterpret_cast<float*>(workspace);
@@ -522,7 +512,7 @@ int mgs_attention_backward(const MgsAttentionArgs* a, const float* out, const fl
   hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, k);
   ATT_LAUNCH(attn_dq_kernel, a->Nq, drop, s, k);
   ATT_LAUNCH(attn_dkv_kernel, a->Nk, drop, s, k);
-  return attn_done(fn);
+  return launch_done(fn);
 }
 
 int mgs_attention_dropout_mask(const MgsAttentionArgs* a, uint8_t* keep, mgs_stream_t stream) {
@@ -538,7 +528,7 @@ int mgs_attention_dropout_mask(const MgsAttentionArgs* a, uint8_t* keep, mgs_str
   AttnK k = attn_args(a);
   hipLaunchKernelGGL(attn_mask_kernel, dim3((unsigned)(a->B * a->H * a->Nq), (a->Nk + 255) / 256), dim3(256), 0,
                      (hipStream_t)stream, k, keep);
-  return attn_done(fn);
+  return launch_done(fn);
 }
 
 }  // extern "C"

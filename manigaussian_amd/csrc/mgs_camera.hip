@@ -136,9 +136,7 @@ int mgs_novel_calib(int V, const float* c2w, const float* K, int W, int H, float
   if (rc || V == 0) return rc;
   hipLaunchKernelGGL(novel_calib_kernel, dim3((V + 63) / 64), dim3(64), 0, (hipStream_t)stream, a, c2w, K,
                      world_view_transform, full_proj_transform, camera_center, fov, tanfov, (int*)singular);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("novel_calib: %s", hipGetErrorString(e)); return MGS_ERR_HIP; }
-  return MGS_OK;
+  return launch_done("novel_calib");
 }
 
 int mgs_novel_calib_host(int V, const float* c2w, const float* K, int W, int H, float znear, float zfar, float trans_x,

@@ -235,6 +235,10 @@ int profile_level();
 
 // ---- launch wrappers (one per .hip translation unit) --------------------------------------------
 void set_error(const char* fmt, ...);
+// the three checks every entry point's host code shares (defined beside set_error in mgs_api.hip)
+int launch_done(const char* fn);          // after the launches: MGS_OK, or "<fn>: <hipGetLastError's text>" and MGS_ERR_HIP
+bool misaligned16(const void* p);         // p is not 16-byte aligned
+int workspace_short(const char* fn, size_t have, size_t need);  // MGS_OK, or the message and MGS_ERR_WORKSPACE when have < need
 
 constexpr int MAX_VIEWS = 16;
 struct ViewCam {  // per-view camera of a multi-view batch

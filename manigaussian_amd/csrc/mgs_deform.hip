@@ -120,9 +120,7 @@ int mgs_deform_assemble_forward(int N, int DL, int DZ, int DA, const float* poin
   hipLaunchKernelGGL(deform_assemble_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, total, stride,
                      DL, DZ, DA, feature ? 1 : 0, point_latent, xyz, sh, rot, scale, opacity, feature, z_feature, action,
                      out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("deform_assemble_fwd: %s", hipGetErrorString(e)); return MGS_ERR_HIP; }
-  return MGS_OK;
+  return launch_done("deform_assemble_fwd");
 }
 
 int mgs_deform_assemble_backward(int N, int DL, int DZ, int DA, int has_feature, const float* g_out,
@@ -135,9 +133,7 @@ int mgs_deform_assemble_backward(int N, int DL, int DZ, int DA, int has_feature,
   const size_t total = (size_t)N * (DL + DZ);
   hipLaunchKernelGGL(deform_assemble_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (size_t)N,
                      stride, DL, DZ, o_z, g_out, g_point_latent, g_z_feature);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("deform_assemble_bwd: %s", hipGetErrorString(e)); return MGS_ERR_HIP; }
-  return MGS_OK;
+  return launch_done("deform_assemble_bwd");
 }
 
 int mgs_deform_apply_forward(int N, const float* xyz, const float* rot, const float* delta, float* xyz_out,
@@ -147,9 +143,7 @@ int mgs_deform_apply_forward(int N, const float* xyz, const float* rot, const fl
   if (!xyz || !rot || !delta || !xyz_out || !rot_out) { set_error("deform_apply: NULL pointer"); return MGS_ERR_INVALID_ARG; }
   hipLaunchKernelGGL(deform_apply_fwd_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, N, xyz, rot,
                      delta, xyz_out, rot_out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("deform_apply_fwd: %s", hipGetErrorString(e)); return MGS_ERR_HIP; }
-  return MGS_OK;
+  return launch_done("deform_apply_fwd");
 }
 
 int mgs_deform_apply_backward(int N, const float* rot, const float* delta, const float* g_xyz_out,
@@ -159,9 +153,7 @@ int mgs_deform_apply_backward(int N, const float* rot, const float* delta, const
   if (!rot || !delta || !g_xyz_out || !g_rot_out || !g_delta) { set_error("deform_apply_bwd: NULL pointer"); return MGS_ERR_INVALID_ARG; }
   hipLaunchKernelGGL(deform_apply_bwd_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, N, rot, delta,
                      g_xyz_out, g_rot_out, g_delta);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("deform_apply_bwd: %s", hipGetErrorString(e)); return MGS_ERR_HIP; }
-  return MGS_OK;
+  return launch_done("deform_apply_bwd");
 }
 
 }  // extern "C"

@@ -382,8 +382,6 @@ __global__ void __launch_bounds__(LOSS_WG) render_loss_bwd_kernel(const float* _
   }
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // Validates a target's strides ([V,C,H,W] in elements) and picks how the 16-byte path reads it.
 static int fill_target(LossTarget& t, const float* p, const int64_t* st, int V, int C, int W, int H, bool vec, const char* what) {
   if (!p || !st) { set_error("render_loss_fwd: %s is NULL", what); return MGS_ERR_INVALID_ARG; }
@@ -397,7 +395,7 @@ static int fill_target(LossTarget& t, const float* p, const int64_t* st, int V, 
   t.p = p;
   t.sv = (int)st[0]; t.sc = (int)st[1]; t.sh = (int)st[2]; t.sw = (int)st[3];
   t.mode = TGT_STRIDED;
-  const bool rows16 = aligned16(p) && (V == 1 || st[0] % 4 == 0) && (H == 1 || st[2] % 4 == 0);
+  const bool rows16 = !misaligned16(p) && (V == 1 || st[0] % 4 == 0) && (H == 1 || st[2] % 4 == 0);
   if (vec && rows16) {
     if (st[3] == 1 && (C == 1 || st[1] % 4 == 0)) t.mode = TGT_PLANAR4;
     else if (C == 3 && st[3] == 3 && st[1] == 1) t.mode = TGT_RGB_PACKED;
@@ -452,16 +450,13 @@ int mgs_render_loss_forward(int V, int F, int W, int H, const float* color, cons
     set_error("%s: unknown embed_fn %d", fn, embed_fn);
     return MGS_ERR_INVALID_ARG;
   }
-  if (workspace_bytes < mgs_render_loss_workspace_bytes(V, W, H)) {
-    set_error("%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, mgs_render_loss_workspace_bytes(V, W, H));
-    return MGS_ERR_WORKSPACE;
-  }
+  if (int rc = workspace_short(fn, workspace_bytes, mgs_render_loss_workspace_bytes(V, W, H))) return rc;
   LossArgs a = {};
   a.V = V; a.F = has_embed ? F : 0; a.W = W; a.H = H; a.N = W * H;
   a.B = (a.N + LOSS_SPAN - 1) / LOSS_SPAN;
   a.embed_fn = has_embed ? embed_fn : -1;
-  a.vec = (W % 4 == 0) && aligned16(color) && (!g_color || aligned16(g_color)) &&
-          (!has_embed || (aligned16(feature) && (!g_feature || aligned16(g_feature))));
+  a.vec = (W % 4 == 0) && !misaligned16(color) && (!g_color || !misaligned16(g_color)) &&
+          (!has_embed || (!misaligned16(feature) && (!g_feature || !misaligned16(g_feature))));
   a.color = color; a.feature = has_embed ? feature : nullptr;
   if (int rc = fill_target(a.rgb, gt_rgb, rgb_strides, V, 3, W, H, a.vec, "gt_rgb")) return rc;
   if (has_embed) {
@@ -483,9 +478,7 @@ int mgs_render_loss_forward(int V, int F, int W, int H, const float* color, cons
   for (int i = 0; i < 2 * V; i++) f.w[i] = a.w[i];
   f.terms = terms; f.loss = loss;
   hipLaunchKernelGGL(render_loss_finalize_kernel, dim3(1), dim3(LOSS_WG), 0, s, f);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("%s: %s", fn, hipGetErrorString(e)); return MGS_ERR_HIP; }
-  return MGS_OK;
+  return launch_done(fn);
 }
 
 int mgs_render_loss_backward(int V, int F, int W, int H, const float* g_up, const float* unit_color, const float* unit_feature,
@@ -501,12 +494,10 @@ int mgs_render_loss_backward(int V, int F, int W, int H, const float* g_up, cons
   const size_t n_c = out_color ? (size_t)V * 3 * N : 0, n_f = (out_feature && F > 0) ? (size_t)V * F * N : 0;
   const size_t quads = (n_c + 3) / 4 + (n_f + 3) / 4;
   if (quads == 0) return MGS_OK;
-  const int vec = (!n_c || (aligned16(unit_color) && aligned16(out_color))) && (!n_f || (aligned16(unit_feature) && aligned16(out_feature)));
+  const int vec = (!n_c || (!misaligned16(unit_color) && !misaligned16(out_color))) && (!n_f || (!misaligned16(unit_feature) && !misaligned16(out_feature)));
   hipLaunchKernelGGL(render_loss_bwd_kernel, dim3((unsigned)((quads + LOSS_WG - 1) / LOSS_WG)), dim3(LOSS_WG), 0,
                      (hipStream_t)stream, g_up, unit_color, out_color, n_c, unit_feature, out_feature, n_f, vec);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("%s: %s", fn, hipGetErrorString(e)); return MGS_ERR_HIP; }
-  return MGS_OK;
+  return launch_done(fn);
 }
 
 }  // extern "C"

@@ -85,9 +85,7 @@ int mgs_mlp_relu_bias(int M, int N, const float* x, const float* bias, float* re
   const int grid = (int)std::min<size_t>((total4 + 255) / 256, 256 * 16);
   hipLaunchKernelGGL(mlp_relu_bias_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, total4, N / 4, (const float4*)x,
                      (const float4*)bias, (float4*)relu_out, (float4*)xb_out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("mlp_relu_bias: %s", hipGetErrorString(e)); return MGS_ERR_HIP; }
-  return MGS_OK;
+  return launch_done("mlp_relu_bias");
 }
 
 int mgs_mlp_relu_backward(int M, int N, const float* g_pre, const float* act, const float* g_res, float* g_out,
@@ -98,9 +96,7 @@ int mgs_mlp_relu_backward(int M, int N, const float* g_pre, const float* act, co
   const int grid = (M + MLP_ROWS - 1) / MLP_ROWS;
   hipLaunchKernelGGL(mlp_relu_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, M, N / 4, (const float4*)g_pre,
                      (const float4*)act, (const float4*)g_res, (float4*)g_out, colsum);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("mlp_relu_backward: %s", hipGetErrorString(e)); return MGS_ERR_HIP; }
-  return MGS_OK;
+  return launch_done("mlp_relu_backward");
 }
 
 }  // extern "C"

@@ -194,10 +194,7 @@ int mgs_lamb_step(int n_tensors, int n_groups, int64_t n_chunks, const MgsLambTe
     set_error("%s: the moment buffers, the tables and the workspace must be 16-byte aligned", fn);
     return MGS_ERR_INVALID_ARG;
   }
-  if (workspace_bytes < mgs_lamb_workspace_bytes(n_chunks)) {
-    set_error("%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, mgs_lamb_workspace_bytes(n_chunks));
-    return MGS_ERR_WORKSPACE;
-  }
+  if (int rc = workspace_short(fn, workspace_bytes, mgs_lamb_workspace_bytes(n_chunks))) return rc;
   LambArgs a = {};
   a.tensors = tensors; a.groups = groups; a.chunk_map = reinterpret_cast<const int2*>(chunk_map);
   a.m = exp_avg; a.v = exp_avg_sq; a.stats = stats; a.partials = reinterpret_cast<float2*>(workspace);
@@ -205,9 +202,7 @@ int mgs_lamb_step(int n_tensors, int n_groups, int64_t n_chunks, const MgsLambTe
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(lamb_moments_kernel, dim3((unsigned)n_chunks), dim3(LAMB_WG), 0, s, a);
   hipLaunchKernelGGL(lamb_apply_kernel, dim3((unsigned)n_chunks), dim3(LAMB_WG), 0, s, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("%s: %s", fn, hipGetErrorString(e)); return MGS_ERR_HIP; }
-  return MGS_OK;
+  return launch_done(fn);
 }
 
 }  // extern "C"

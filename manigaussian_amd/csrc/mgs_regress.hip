@@ -132,9 +132,7 @@ int mgs_regress_epilogue_forward(int N, const float* raw, const float* xyz_in, f
   }
   hipLaunchKernelGGL(regress_epilogue_fwd_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, N, raw, xyz_in,
                      xyz, opacity, scale, rot, sh, feature, feature_n);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("regress_epilogue_fwd: %s", hipGetErrorString(e)); return MGS_ERR_HIP; }
-  return MGS_OK;
+  return launch_done("regress_epilogue_fwd");
 }
 
 int mgs_regress_epilogue_backward(int N, const float* raw, const float* g_xyz, const float* g_opacity, const float* g_scale,
@@ -145,9 +143,7 @@ int mgs_regress_epilogue_backward(int N, const float* raw, const float* g_xyz, c
   if (!raw || !g_raw) { set_error("regress_epilogue_bwd: NULL pointer"); return MGS_ERR_INVALID_ARG; }
   hipLaunchKernelGGL(regress_epilogue_bwd_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, N, raw, g_xyz,
                      g_opacity, g_scale, g_rot, g_sh, g_feature, g_feature_n, g_raw);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("regress_epilogue_bwd: %s", hipGetErrorString(e)); return MGS_ERR_HIP; }
-  return MGS_OK;
+  return launch_done("regress_epilogue_bwd");
 }
 
 }  // extern "C"

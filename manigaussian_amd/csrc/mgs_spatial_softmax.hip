@@ -373,8 +373,6 @@ static int ss_auto_slices(int64_t rows, int64_t N) {
   return s < 1 ? 1 : (int)s;
 }
 
-static bool ss_misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
-
 // sizes, temperature and the split, common to forward and backward -> g
 static int ss_check(const char* fn, int64_t rows, int C, int D, int H, int W, float temperature, int slices, SsGeom* g) {
   if (rows < 1 || C < 1 || D < 1 || H < 1 || W < 1) {
@@ -412,12 +410,6 @@ static int ss_check(const char* fn, int64_t rows, int C, int D, int H, int W, fl
   return MGS_OK;
 }
 
-static int ss_done(const char* fn) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("%s: %s", fn, hipGetErrorString(e)); return MGS_ERR_HIP; }
-  return MGS_OK;
-}
-
 }  // namespace mgs
 
 using namespace mgs;
@@ -440,7 +432,7 @@ int mgs_spatial_softmax_forward(int64_t rows, int C, int D, int H, int W, float 
     set_error("%s: NULL feature, keypoints, stats or workspace", fn);
     return MGS_ERR_INVALID_ARG;
   }
-  if (ss_misaligned(feature) || ss_misaligned(workspace)) {
+  if (misaligned16(feature) || misaligned16(workspace)) {
     set_error("%s: feature and the workspace must be 16-byte aligned", fn);
     return MGS_ERR_INVALID_ARG;
   }
@@ -450,10 +442,7 @@ int mgs_spatial_softmax_forward(int64_t rows, int C, int D, int H, int W, float 
     return MGS_ERR_INVALID_ARG;
   }
   const size_t need = mgs_spatial_softmax_workspace_bytes(rows, g.N);
-  if (workspace_bytes < need) {
-    set_error("%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, need);
-    return MGS_ERR_WORKSPACE;
-  }
+  if (int rc = workspace_short(fn, workspace_bytes, need)) return rc;
   hipStream_t s = (hipStream_t)stream;
   float* records = reinterpret_cast<float*>(workspace);
   const dim3 grid((unsigned)(rows * g.slices));
@@ -461,7 +450,7 @@ int mgs_spatial_softmax_forward(int64_t rows, int C, int D, int H, int W, float 
   else hipLaunchKernelGGL((ss_fwd_kernel<false>), grid, dim3(SS_THREADS), 0, s, g, feature, records);
   hipLaunchKernelGGL(ss_combine_kernel, dim3((unsigned)((rows + SS_THREADS - 1) / SS_THREADS)), dim3(SS_THREADS), 0, s, g,
                      (uint32_t)rows, records, keypoints, keypoints_stride_b, maxpool, maxpool_stride_b, stats);
-  return ss_done(fn);
+  return launch_done(fn);
 }
 
 int mgs_spatial_softmax_backward(int64_t rows, int C, int D, int H, int W, float temperature, const float* feature,
@@ -472,7 +461,7 @@ int mgs_spatial_softmax_backward(int64_t rows, int C, int D, int H, int W, float
   int rc = ss_check(fn, rows, C, D, H, W, temperature, slices, &g);
   if (rc != MGS_OK) return rc;
   if (!feature || !stats || !g_feature) { set_error("%s: NULL feature, stats or g_feature", fn); return MGS_ERR_INVALID_ARG; }
-  if (ss_misaligned(feature) || ss_misaligned(g_feature)) {
+  if (misaligned16(feature) || misaligned16(g_feature)) {
     set_error("%s: feature and g_feature must be 16-byte aligned", fn);
     return MGS_ERR_INVALID_ARG;
   }
@@ -489,7 +478,7 @@ int mgs_spatial_softmax_backward(int64_t rows, int C, int D, int H, int W, float
   else
     hipLaunchKernelGGL((ss_bwd_kernel<false>), grid, dim3(SS_THREADS), 0, s, g, feature, stats, g_keypoints, g_keypoints_stride_b,
                        g_max, g_max_stride_b, g_feature);
-  return ss_done(fn);
+  return launch_done(fn);
 }
 
 }  // extern "C"

@@ -383,12 +383,6 @@ static size_t vol_workspace(const MgsVolumeArgs* a, int64_t Ct) {
 
 static unsigned vol_blocks(int64_t lanes) { return (unsigned)((lanes + VOL_THREADS - 1) / VOL_THREADS); }
 
-static int vol_done(const char* fn) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("%s: %s", fn, hipGetErrorString(e)); return MGS_ERR_HIP; }
-  return MGS_OK;
-}
-
 }  // namespace mgs
 
 using namespace mgs;
@@ -420,7 +414,7 @@ int mgs_volume_resample_pad_forward(const MgsVolumeArgs* a, float* out, mgs_stre
   hipStream_t s = (hipStream_t)stream;
   if (a->scale == 1) hipLaunchKernelGGL((vol_fwd_kernel<true>), grid, block, 0, s, g, out);
   else hipLaunchKernelGGL((vol_fwd_kernel<false>), grid, block, 0, s, g, out);
-  return vol_done(fn);
+  return launch_done(fn);
 }
 
 int mgs_volume_resample_pad_backward(const MgsVolumeArgs* a, const float* g_out, float* const* g_src, void* workspace,
@@ -441,10 +435,7 @@ int mgs_volume_resample_pad_backward(const MgsVolumeArgs* a, const float* g_out,
     return MGS_ERR_INVALID_ARG;
   }
   const size_t need = vol_workspace(a, Ct);
-  if (workspace_bytes < need) {
-    set_error("%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, need);
-    return MGS_ERR_INVALID_ARG;
-  }
+  if (workspace_short(fn, workspace_bytes, need)) return MGS_ERR_INVALID_ARG;  // (this entry point's code for it)
   if (a->B == 0) return MGS_OK;
   VolGeom g;
   vol_geom(a, Ct, &g);
@@ -469,7 +460,7 @@ int mgs_volume_resample_pad_backward(const MgsVolumeArgs* a, const float* g_out,
     g.total = (uint32_t)in_elems;
     hipLaunchKernelGGL(vol_bwd_z_kernel, dim3(vol_blocks(most), (unsigned)a->nsrc), block, 0, s, g, (const float*)ws);
   }
-  return vol_done(fn);
+  return launch_done(fn);
 }
 
 }  // extern "C"

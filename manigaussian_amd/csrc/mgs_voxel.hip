@@ -123,9 +123,7 @@ int mgs_voxel_sample_pe_forward(int N, int C, int D, int H, int W, int K, float 
   const size_t total = (size_t)N * (C + 3 + 6 * K);
   const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
   hipLaunchKernelGGL(voxel_sample_pe_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, voxel, xyz, out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("voxel_sample_fwd: %s", hipGetErrorString(e)); return MGS_ERR_HIP; }
-  return MGS_OK;
+  return launch_done("voxel_sample_fwd");
 }
 
 int mgs_voxel_sample_backward(int N, int C, int D, int H, int W, const float* bounds_host, const float* xyz,
@@ -139,9 +137,7 @@ int mgs_voxel_sample_backward(int N, int C, int D, int H, int W, const float* bo
   const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
   hipLaunchKernelGGL(voxel_sample_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, xyz, g_out, row_stride,
                      g_voxel);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("voxel_sample_bwd: %s", hipGetErrorString(e)); return MGS_ERR_HIP; }
-  return MGS_OK;
+  return launch_done("voxel_sample_bwd");
 }
 
 }  // extern "C"

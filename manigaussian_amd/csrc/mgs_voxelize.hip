@@ -262,10 +262,7 @@ static int vox_run(const char* fn, int B, int64_t N, int V, int Fc, int channels
                    const VoxInput& feats, int per_src, const float* bounds, float* grid, void* workspace,
                    size_t workspace_bytes, mgs_stream_t stream) {
   const VoxCarve cv = vox_carve(B, N, V);
-  if (workspace_bytes < cv.total) {
-    set_error("%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, cv.total);
-    return MGS_ERR_WORKSPACE;
-  }
+  if (int rc = workspace_short(fn, workspace_bytes, cv.total)) return rc;
   char* ws = reinterpret_cast<char*>(workspace);
   VoxArgs a = {};
   a.B = B; a.N = (int)N; a.V = V; a.Fc = Fc; a.V3 = V * V * V; a.per_src = per_src > 0 ? per_src : 1;
@@ -293,9 +290,7 @@ static int vox_run(const char* fn, int B, int64_t N, int V, int Fc, int channels
     const int64_t total = (int64_t)B * a.V3 * (Fc + 7), threads = (total + 3) / 4;
     hipLaunchKernelGGL(voxelize_write_cl_kernel, dim3((unsigned)((threads + VOX_WG - 1) / VOX_WG)), dim3(VOX_WG), 0, s, a, total);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("%s: %s", fn, hipGetErrorString(e)); return MGS_ERR_HIP; }
-  return MGS_OK;
+  return launch_done(fn);
 }
 
 static int vox_check(const char* fn, int B, int64_t N, int V, int Fc, const float* bounds, const float* grid, const void* workspace) {

@@ -10,17 +10,12 @@ Three pieces:
                               d_out 7, ReLU).  The GEMMs stay in torch (hipBLASLt / MFMA): they are dense
                               contractions, not part of the hand-written path.
 """
-import ctypes
 import os
 
 import torch
 import torch.nn as nn
 
-from . import _lib
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+from . import _lib, _ops
 
 
 def _c(t):
@@ -34,7 +29,6 @@ def _c(t):
 class _AssembleDeformInput(torch.autograd.Function):
     @staticmethod
     def forward(ctx, point_latent, z_feature, xyz, sh, rot, scale, opacity, feature, action):
-        L = _lib.lib()
         dev = point_latent.device
         N, DL = point_latent.shape
         DZ = z_feature.shape[1]
@@ -47,25 +41,22 @@ class _AssembleDeformInput(torch.autograd.Function):
         f = _c(feature.reshape(N, 3)) if has_feat else None
         z = _c(z_feature)
         a = _c(action.reshape(-1)) if DA else None
-        with torch.cuda.device(dev):
-            _lib.check(L.mgs_deform_assemble_forward(
-                N, DL, DZ, DA, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), t[4].data_ptr(),
-                t[5].data_ptr(), f.data_ptr() if has_feat else None, z.data_ptr(), a.data_ptr() if DA else None,
-                out.data_ptr(), _stream(dev)), "deform_assemble_forward")
+        _ops.call("mgs_deform_assemble_forward", dev,
+                  N, DL, DZ, DA, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), t[4].data_ptr(),
+                  t[5].data_ptr(), f.data_ptr() if has_feat else None, z.data_ptr(), a.data_ptr() if DA else None,
+                  out.data_ptr())
         ctx.dims = (N, DL, DZ, DA, has_feat)
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        L = _lib.lib()
         N, DL, DZ, DA, has_feat = ctx.dims
         dev = g_out.device
         g_out = _c(g_out)
         g_lat = torch.empty((N, DL), dtype=torch.float32, device=dev)
         g_z = torch.empty((N, DZ), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.mgs_deform_assemble_backward(N, DL, DZ, DA, int(has_feat), g_out.data_ptr(), g_lat.data_ptr(),
-                                                      g_z.data_ptr(), _stream(dev)), "deform_assemble_backward")
+        _ops.call("mgs_deform_assemble_backward", dev, N, DL, DZ, DA, int(has_feat), g_out.data_ptr(), g_lat.data_ptr(),
+                  g_z.data_ptr())
         # everything but point_latent and z_feature is .detach()ed in the reference
         return g_lat, g_z, None, None, None, None, None, None, None
 
@@ -79,32 +70,26 @@ def assemble_deform_input(point_latent, z_feature, xyz, sh, rot, scale, opacity,
 class _DeformApply(torch.autograd.Function):
     @staticmethod
     def forward(ctx, delta, xyz, rot):
-        L = _lib.lib()
         dev = delta.device
         N = delta.shape[0]
         delta, xyz, rot = _c(delta), _c(xyz.reshape(N, 3)), _c(rot.reshape(N, 4))
         xyz_out = torch.empty((N, 3), dtype=torch.float32, device=dev)
         rot_out = torch.empty((N, 4), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.mgs_deform_apply_forward(N, xyz.data_ptr(), rot.data_ptr(), delta.data_ptr(),
-                                                  xyz_out.data_ptr(), rot_out.data_ptr(), _stream(dev)),
-                       "deform_apply_forward")
+        _ops.call("mgs_deform_apply_forward", dev, N, xyz.data_ptr(), rot.data_ptr(), delta.data_ptr(),
+                  xyz_out.data_ptr(), rot_out.data_ptr())
         ctx.save_for_backward(delta, rot)
         return xyz_out, rot_out
 
     @staticmethod
     def backward(ctx, g_xyz, g_rot):
-        L = _lib.lib()
         delta, rot = ctx.saved_tensors
         dev = delta.device
         N = delta.shape[0]
         g_xyz = _c(g_xyz) if g_xyz is not None else torch.zeros((N, 3), dtype=torch.float32, device=dev)
         g_rot = _c(g_rot) if g_rot is not None else torch.zeros((N, 4), dtype=torch.float32, device=dev)
         g_delta = torch.empty((N, 7), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.mgs_deform_apply_backward(N, rot.data_ptr(), delta.data_ptr(), g_xyz.data_ptr(),
-                                                   g_rot.data_ptr(), g_delta.data_ptr(), _stream(dev)),
-                       "deform_apply_backward")
+        _ops.call("mgs_deform_apply_backward", dev, N, rot.data_ptr(), delta.data_ptr(), g_xyz.data_ptr(),
+                  g_rot.data_ptr(), g_delta.data_ptr())
         return g_delta, None, None
 
 
@@ -162,7 +147,7 @@ def _relu_bias(x, bias, want_relu=True, want_xb=True):
     xb = torch.empty_like(x) if want_xb else None
     _lib.check(_lib.lib().mgs_mlp_relu_bias(M, N, x.data_ptr(), 0 if bias is None else bias.data_ptr(),
                                             0 if a is None else a.data_ptr(), 0 if xb is None else xb.data_ptr(),
-                                            _stream(x.device)), "mgs_mlp_relu_bias")
+                                            _ops.stream(x.device)), "mgs_mlp_relu_bias")
     return a, xb
 
 
@@ -171,7 +156,7 @@ def _relu_backward(g_pre, act, g_res, colsum):
     M, N = g_pre.shape
     _lib.check(_lib.lib().mgs_mlp_relu_backward(M, N, g_pre.data_ptr(), act.data_ptr(),
                                                 0 if g_res is None else g_res.data_ptr(), g_pre.data_ptr(),
-                                                0 if colsum is None else colsum.data_ptr(), _stream(g_pre.device)),
+                                                0 if colsum is None else colsum.data_ptr(), _ops.stream(g_pre.device)),
                "mgs_mlp_relu_backward")
     return g_pre
 

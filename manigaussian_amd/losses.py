@@ -10,14 +10,10 @@ import ctypes
 
 import torch
 
-from . import _lib
+from . import _lib, _ops
 
 EMBED_FNS = {"cosine": 0, "l2": 1, "l2_norm": 2}
 MAX_F = 64
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _images(t, name, channels=None):
@@ -96,13 +92,12 @@ class _RenderingLoss(torch.autograd.Function):
         loss = buf[n_c + n_f + n_ws + 3 * V:].view(())
         i64x4 = ctypes.c_int64 * 4
         wh = (ctypes.c_float * (2 * V))(*w_host) if w_host is not None else None
-        with torch.cuda.device(dev):
-            _lib.check(L.mgs_render_loss_forward(
-                V, F, W, H, color.data_ptr(), gt_rgb.data_ptr(), i64x4(*rgb_st),
-                feature.data_ptr() if has_embed else None, gt_embed.data_ptr() if has_embed else None,
-                i64x4(*emb_st) if has_embed else None, embed_fn, wh, None if w_dev is None else w_dev.data_ptr(),
-                g_color.data_ptr() if need_c else None, g_feature.data_ptr() if need_f else None, terms.data_ptr(),
-                loss.data_ptr(), ws.data_ptr(), ws_bytes, _stream(dev)), "render_loss_forward")
+        _ops.call("mgs_render_loss_forward", dev,
+                  V, F, W, H, color.data_ptr(), gt_rgb.data_ptr(), i64x4(*rgb_st),
+                  feature.data_ptr() if has_embed else None, gt_embed.data_ptr() if has_embed else None,
+                  i64x4(*emb_st) if has_embed else None, embed_fn, wh, _ops.ptr(w_dev),
+                  g_color.data_ptr() if need_c else None, g_feature.data_ptr() if need_f else None, terms.data_ptr(),
+                  loss.data_ptr(), ws.data_ptr(), ws_bytes)
         ctx.unit = (g_color if need_c else None, g_feature if need_f else None)
         ctx.shape = (V, F, W, H)
         ctx.mark_non_differentiable(terms)
@@ -114,7 +109,6 @@ class _RenderingLoss(torch.autograd.Function):
     def backward(ctx, g_loss, _g_terms):
         if g_loss is None:
             return (None,) * 9
-        L = _lib.lib()
         V, F, W, H = ctx.shape
         unit_c, unit_f = ctx.unit
         dev = g_loss.device
@@ -122,10 +116,8 @@ class _RenderingLoss(torch.autograd.Function):
         out_c = torch.empty((V, 3, H, W), dtype=torch.float32, device=dev) if unit_c is not None else None
         out_f = torch.empty((V, F, H, W), dtype=torch.float32, device=dev) if unit_f is not None else None
         if out_c is not None or out_f is not None:
-            p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-            with torch.cuda.device(dev):
-                _lib.check(L.mgs_render_loss_backward(V, F, W, H, g_up.data_ptr(), p(unit_c), p(unit_f), p(out_c), p(out_f),
-                                                      _stream(dev)), "render_loss_backward")
+            p = _ops.ptr
+            _ops.call("mgs_render_loss_backward", dev, V, F, W, H, g_up.data_ptr(), p(unit_c), p(unit_f), p(out_c), p(out_f))
         return (out_c, out_f) + (None,) * 7
 
 

@@ -10,12 +10,10 @@ The algorithm is the reference's, quirks included: no bias correction, the weigh
 where either norm is exactly zero, `adam=True` applies ratio 1 but records the computed one, a parameter without a gradient
 is skipped entirely.
 """
-import ctypes
-
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _ops
 
 _TENSOR_DT = np.dtype([("p", "<u8"), ("g", "<u8"), ("numel", "<i8"), ("state_off", "<i8"), ("group", "<i4"), ("flags", "<i4"),
                        ("chunk0", "<i4"), ("n_chunks", "<i4")])     # MgsLambTensor (include/mgsplat.h)
@@ -303,13 +301,9 @@ class FusedLamb(torch.optim.Optimizer):
                 self._bind_state(lay["params"][i], 1)
             else:
                 st["step"] += 1
-        L = _lib.lib()
-        dev = lay["dev"]
         base = lay["table"].data_ptr()
-        with torch.cuda.device(dev):
-            _lib.check(L.mgs_lamb_step(
-                len(lay["params"]), len(self.param_groups), lay["total_chunks"], base, base + lay["t_bytes"],
-                base + lay["t_bytes"] + lay["g_bytes"], lay["m"].data_ptr(), lay["v"].data_ptr(), lay["stats"].data_ptr(),
-                self.grad_scale, int(self.fused_zero_grad), lay["ws"].data_ptr(), lay["ws_bytes"],
-                ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "lamb_step")
+        _ops.call("mgs_lamb_step", lay["dev"],
+                  len(lay["params"]), len(self.param_groups), lay["total_chunks"], base, base + lay["t_bytes"],
+                  base + lay["t_bytes"] + lay["g_bytes"], lay["m"].data_ptr(), lay["v"].data_ptr(), lay["stats"].data_ptr(),
+                  self.grad_scale, int(self.fused_zero_grad), lay["ws"].data_ptr(), lay["ws_bytes"])
         return loss

@@ -5,23 +5,16 @@ f_dc 3, feature 3, f_rest 9), scale = clamp_max(exp(.), 0.05), opacity = sigmoid
 [N,4,3], xyz = xyz_in + delta -- and agents/manigaussian_bc/gaussian_renderer/__init__.py:66-68 -- the language feature is
 L2-normalised with a 1e-12 guard right before rasterization.  ~10 torch kernels + 3 cats there; one HIP pass each way here.
 """
-import ctypes
-
 import torch
 
-from . import _lib
+from . import _ops
 
 RAW_DIM = 26
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 class _Epilogue(torch.autograd.Function):
     @staticmethod
     def forward(ctx, raw, xyz_in):
-        L = _lib.lib()
         if not raw.is_cuda:
             raise RuntimeError("gaussian_epilogue needs tensors on a HIP device; there is no CPU path")
         if raw.size(-1) != RAW_DIM:
@@ -34,10 +27,8 @@ class _Epilogue(torch.autograd.Function):
         o = dict(dtype=torch.float32, device=dev)
         xyz, opacity, scale, rot = torch.empty((N, 3), **o), torch.empty((N, 1), **o), torch.empty((N, 3), **o), torch.empty((N, 4), **o)
         sh, feat, feat_n = torch.empty((N, 4, 3), **o), torch.empty((N, 3), **o), torch.empty((N, 3), **o)
-        with torch.cuda.device(dev):
-            _lib.check(L.mgs_regress_epilogue_forward(N, r.data_ptr(), x.data_ptr(), xyz.data_ptr(), opacity.data_ptr(),
-                                                      scale.data_ptr(), rot.data_ptr(), sh.data_ptr(), feat.data_ptr(),
-                                                      feat_n.data_ptr(), _stream(dev)), "regress_epilogue_forward")
+        _ops.call("mgs_regress_epilogue_forward", dev, N, r.data_ptr(), x.data_ptr(), xyz.data_ptr(), opacity.data_ptr(),
+                  scale.data_ptr(), rot.data_ptr(), sh.data_ptr(), feat.data_ptr(), feat_n.data_ptr())
         ctx.save_for_backward(r)
         ctx.lead = lead
         ctx.set_materialize_grads(False)
@@ -46,16 +37,14 @@ class _Epilogue(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_xyz, g_opacity, g_scale, g_rot, g_sh, g_feat, g_feat_n):
-        L = _lib.lib()
         (r,) = ctx.saved_tensors
         dev = r.device
         N = r.size(0)
         c = lambda t: None if t is None else t.float().contiguous()  # noqa: E731
         gs = [c(g_xyz), c(g_opacity), c(g_scale), c(g_rot), c(g_sh), c(g_feat), c(g_feat_n)]
         g_raw = torch.empty((N, RAW_DIM), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.mgs_regress_epilogue_backward(N, r.data_ptr(), *[None if t is None else t.data_ptr() for t in gs],
-                                                       g_raw.data_ptr(), _stream(dev)), "regress_epilogue_backward")
+        _ops.call("mgs_regress_epilogue_backward", dev, N, r.data_ptr(), *[None if t is None else t.data_ptr() for t in gs],
+                  g_raw.data_ptr())
         g_in = None if g_xyz is None else g_xyz  # xyz = xyz_in + delta
         return g_raw.reshape(*ctx.lead, RAW_DIM), g_in
 

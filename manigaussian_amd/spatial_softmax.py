@@ -13,31 +13,13 @@ Capturable into a HIP graph.
 
 There is no CPU path.
 """
-import ctypes
-
 import numpy as np
 import torch
 from torch import nn
 
-from . import _lib
+from . import _lib, _ops
 
 STATS = 6  # floats per (batch, channel): max, sum, E_x, E_y, E_z, argmax (the bits of a uint32)
-
-_WORKSPACES = {}  # (device index, bytes) -> uint8 tensor (the slice records: written by every forward before it reads them)
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _workspace(dev, rows, n):
-    size = _lib.lib().mgs_spatial_softmax_workspace_bytes(rows, n)
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), size)
-    ws = _WORKSPACES.get(key)
-    if ws is None:
-        ws = _WORKSPACES[key] = torch.empty(size, dtype=torch.uint8, device=dev)
-    return ws
-
 
 def _readable(t):
     """The tensor itself when the kernels can read it in place (contiguous, 16-byte aligned), else one contiguous copy."""
@@ -62,13 +44,12 @@ class _SpatialSoftmax3D(torch.autograd.Function):
         rows, n = B * C, D * H * W
         out = torch.empty(B, 4 * C, dtype=torch.float32, device=dev)
         stats = torch.empty(rows, STATS, dtype=torch.float32, device=dev)
-        ws = _workspace(dev, rows, n)
+        # the slice records: written by every forward before it reads them
+        ws = _ops.workspace(dev, _lib.lib().mgs_spatial_softmax_workspace_bytes(rows, n))
         keypoints, maxpool = out[:, :3 * C], out[:, 3 * C:]
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().mgs_spatial_softmax_forward(rows, C, D, H, W, temperature, feature.data_ptr(),
-                                                              keypoints.data_ptr(), out.stride(0), maxpool.data_ptr(), out.stride(0),
-                                                              stats.data_ptr(), ws.data_ptr(), ws.numel(), slices, _stream(dev)),
-                       "spatial_softmax_forward")
+        _ops.call("mgs_spatial_softmax_forward", dev, rows, C, D, H, W, temperature, feature.data_ptr(),
+                  keypoints.data_ptr(), out.stride(0), maxpool.data_ptr(), out.stride(0),
+                  stats.data_ptr(), ws.data_ptr(), ws.numel(), slices)
         ctx.save_for_backward(feature, stats)
         ctx.temperature, ctx.slices = temperature, slices
         ctx.set_materialize_grads(False)
@@ -87,14 +68,9 @@ class _SpatialSoftmax3D(torch.autograd.Function):
             gk = _rows_by_stride(g_keypoints.to(torch.float32))
         if g_max is not None:
             gm = _rows_by_stride(g_max.to(torch.float32))
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().mgs_spatial_softmax_backward(B * C, C, D, H, W, ctx.temperature, feature.data_ptr(), stats.data_ptr(),
-                                                               gk.data_ptr() if gk is not None else None,
-                                                               gk.stride(0) if gk is not None else 0,
-                                                               gm.data_ptr() if gm is not None else None,
-                                                               gm.stride(0) if gm is not None else 0,
-                                                               g_feature.data_ptr(), ctx.slices, _stream(dev)),
-                       "spatial_softmax_backward")
+        _ops.call("mgs_spatial_softmax_backward", dev, B * C, C, D, H, W, ctx.temperature, feature.data_ptr(), stats.data_ptr(),
+                  _ops.ptr(gk), gk.stride(0) if gk is not None else 0, _ops.ptr(gm), gm.stride(0) if gm is not None else 0,
+                  g_feature.data_ptr(), ctx.slices)
         return g_feature, None, None
 
 

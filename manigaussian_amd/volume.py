@@ -19,26 +19,10 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _lib
+from . import _lib, _ops
 
 LRELU_SLOPE = 0.02
 MAX_SOURCES, MAX_SCALE, MAX_PAD = _lib.VOLUME_MAX_SOURCES, 8, 8
-
-_WORKSPACES = {}  # (device index, bytes) -> uint8 tensor (the backward's x y sums; written before they are read in every call)
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _workspace(dev, args):
-    n = _lib.lib().mgs_volume_workspace_bytes(ctypes.byref(args))
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), n)
-    ws = _WORKSPACES.get(key)
-    if ws is None:
-        ws = _WORKSPACES[key] = torch.empty(n, dtype=torch.uint8, device=dev)
-    return ws
-
 
 def _in_place(t):
     """The tensor itself when the kernels can read it where it lies -- spatial dimensions contiguous, batch and channel strides
@@ -80,9 +64,7 @@ class _ResamplePad(torch.autograd.Function):
             a.src[k], a.stride_b[k], a.stride_c[k] = t.data_ptr(), t.stride(0), t.stride(1)
         out = torch.empty(B, sum(s[1] for s in shapes), scale * D + 2 * pad, scale * H + 2 * pad, scale * W + 2 * pad,
                           dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().mgs_volume_resample_pad_forward(ctypes.byref(a), out.data_ptr(), _stream(dev)),
-                       "volume_resample_pad_forward")
+        _ops.call("mgs_volume_resample_pad_forward", dev, ctypes.byref(a), out.data_ptr())
         ctx.shapes, ctx.scale, ctx.pad = shapes, scale, pad  # (a linear op: its gradient needs no tensor of the forward)
         return out
 
@@ -93,11 +75,9 @@ class _ResamplePad(torch.autograd.Function):
         a = _args(ctx.shapes, ctx.scale, ctx.pad)
         grads = [torch.empty(s, dtype=torch.float32, device=dev) for s in ctx.shapes]
         pointers = (_lib.c_fp * len(grads))(*[g.data_ptr() for g in grads])
-        ws = _workspace(dev, a)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().mgs_volume_resample_pad_backward(ctypes.byref(a), g_out.data_ptr(), pointers, ws.data_ptr(),
-                                                                   ws.numel(), _stream(dev)),
-                       "volume_resample_pad_backward")
+        # the x y sums: written before they are read in every call
+        ws = _ops.workspace(dev, _lib.lib().mgs_volume_workspace_bytes(ctypes.byref(a)))
+        _ops.call("mgs_volume_resample_pad_backward", dev, ctypes.byref(a), g_out.data_ptr(), pointers, ws.data_ptr(), ws.numel())
         return (None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:]))
 
 

@@ -9,17 +9,12 @@ import ctypes
 
 import torch
 
-from . import _lib
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+from . import _ops
 
 
 class _PointLatent(torch.autograd.Function):
     @staticmethod
     def forward(ctx, voxel, xyz, bounds, num_freqs, freq_factor):
-        L = _lib.lib()
         if not voxel.is_cuda:
             raise RuntimeError("point_latent_pe needs tensors on a HIP device; there is no CPU path")
         if voxel.dim() != 5 or voxel.size(0) != 1:
@@ -31,25 +26,22 @@ class _PointLatent(torch.autograd.Function):
         N = pts.size(0)
         out = torch.empty((N, C + 3 + 6 * num_freqs), dtype=torch.float32, device=dev)
         b = (ctypes.c_float * 6)(*[float(x) for x in bounds])
-        with torch.cuda.device(dev):
-            _lib.check(L.mgs_voxel_sample_pe_forward(N, C, D, H, W, int(num_freqs), float(freq_factor), b, vox.data_ptr(),
-                                                     pts.data_ptr(), out.data_ptr(), _stream(dev)), "voxel_sample_pe_forward")
+        _ops.call("mgs_voxel_sample_pe_forward", dev, N, C, D, H, W, int(num_freqs), float(freq_factor), b, vox.data_ptr(),
+                  pts.data_ptr(), out.data_ptr())
         ctx.save_for_backward(pts)
         ctx.meta = (C, D, H, W, tuple(float(x) for x in bounds), voxel.shape)
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        L = _lib.lib()
         (pts,) = ctx.saved_tensors
         C, D, H, W, bounds, vshape = ctx.meta
         dev = pts.device
         g = g_out.float().contiguous()
         g_vox = torch.zeros(vshape, dtype=torch.float32, device=dev)
         b = (ctypes.c_float * 6)(*bounds)
-        with torch.cuda.device(dev):
-            _lib.check(L.mgs_voxel_sample_backward(pts.size(0), C, D, H, W, b, pts.data_ptr(), g.data_ptr(), g.size(1),
-                                                   g_vox.data_ptr(), _stream(dev)), "voxel_sample_backward")
+        _ops.call("mgs_voxel_sample_backward", dev, pts.size(0), C, D, H, W, b, pts.data_ptr(), g.data_ptr(), g.size(1),
+                  g_vox.data_ptr())
         return g_vox, None, None, None, None
 
 

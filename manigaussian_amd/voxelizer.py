@@ -15,34 +15,27 @@ memory="channels_first" (default): the result is a permuted view of a contiguous
 `voxel_grid.permute(0, 4, 1, 2, 3)` is contiguous and Conv3d copies nothing.  memory="channels_last": contiguous
 [B,V,V,V,C], the reference's layout.
 """
-import ctypes
-
 import torch
 from torch import nn
 
-from . import _lib
+from . import _lib, _ops
 
 MEMORY = ("channels_first", "channels_last")
 MAX_FEATURES = 64  # MGS_VOXELIZE_MAX_FEATURES
 MAX_IMAGES = 8     # MGS_VOXELIZE_MAX_SOURCES
 
-_WORKSPACES = {}  # (device index, B, N, V) -> uint8 tensor; the library zeroes what it needs of it in every call
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+_WS_BYTES = {}  # (B, N, V) -> bytes of the workspace; the library zeroes what it needs of it in every call
 
 
 def _workspace(dev, B, N, V):
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), B, N, V)
-    ws = _WORKSPACES.get(key)
-    if ws is None:
+    n = _WS_BYTES.get((B, N, V))
+    if n is None:
         n = _lib.lib().mgs_voxelize_workspace_bytes(B, N, V)
         if n == 0:
             raise ValueError(f"voxelizer: B = {B}, N = {N}, V = {V} is beyond the library's limits "
                              "(B <= 65536, N <= 2^24, B V^3 and B N below 2^31)")
-        ws = _WORKSPACES[key] = torch.empty(n, dtype=torch.uint8, device=dev)
-    return ws
+        _WS_BYTES[B, N, V] = n
+    return _ops.workspace(dev, n)
 
 
 def _check_memory(memory):
@@ -92,11 +85,8 @@ def voxelize(coords, features, bounds, voxel_size, memory="channels_first"):
     bd = _bounds(bounds, B, dev)
     ws = _workspace(dev, B, N, V)
     grid = _alloc(B, V, Fc + 7, memory, dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mgs_voxelize_forward(B, N, V, Fc, int(memory == "channels_first"), pts.data_ptr() if N else None,
-                                                   fts.data_ptr() if (fts is not None and N) else None, bd.data_ptr(),
-                                                   grid.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
-                   "voxelize_forward")
+    _ops.call("mgs_voxelize_forward", dev, B, N, V, Fc, int(memory == "channels_first"), _ops.ptr(pts), _ops.ptr(fts),
+              bd.data_ptr(), grid.data_ptr(), ws.data_ptr(), ws.numel())
     return _as_reference(grid, memory)
 
 
@@ -126,10 +116,8 @@ def voxelize_images(pcds, rgbs, bounds, voxel_size, memory="channels_first"):
     grid = _alloc(B, V, Fc + 7, memory, dev)
     cp = (_lib.c_fp * n)(*[t.data_ptr() for t in pts])
     fp = (_lib.c_fp * n)(*[t.data_ptr() for t in fts]) if Fc > 0 else None
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mgs_voxelize_forward_images(B, n, H * W, V, Fc, int(memory == "channels_first"), cp, fp,
-                                                          bd.data_ptr(), grid.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                          _stream(dev)), "voxelize_forward_images")
+    _ops.call("mgs_voxelize_forward_images", dev, B, n, H * W, V, Fc, int(memory == "channels_first"), cp, fp,
+              bd.data_ptr(), grid.data_ptr(), ws.data_ptr(), ws.numel())
     return _as_reference(grid, memory)
 
 

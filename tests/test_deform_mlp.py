@@ -141,7 +141,12 @@ def test_deformation_field_on_gpu_matches_reference_fixture(path):
 def test_fused_resnetfc_equals_the_plain_module_on_gpu(M, hidden, use_x):
     """The fused path (hand-issued GEMMs + mgs_mlp.hip elementwise passes, split-K weight gradients in the 8192-row case) and the
     module's plain torch path, both in fp32 with the same non-trivial weights, against the plain path in float64: outputs,
-    input gradient and every parameter gradient -- the fused path must be as close to the exact result as the plain one."""
+    input gradient and every parameter gradient -- the fused path must be as close to the exact result as the plain one.
+    ReLU flips near zero force the quantile bound below, which a short last row group of a column sum could slip through: the
+    row seams and the branches of the backward (g_delta None, frozen parameters, an input that is data, combine_layer 0 or
+    >= n_blocks, one block, other hidden widths) are pinned bit for bit by the integer-valued cases of
+    tests/test_embed_kernels.py (test_fused_resnetfc_is_exact_on_integers), and one real-valued case whose pre-activations keep
+    clear of zero meets the float64 truth element by element there."""
     dev = torch.device("cuda:0")
     torch.manual_seed(M)
     deform._WGRAD_MIN_ROWS = 512 if M == 8192 else 4096

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 13
+#define MGS_ABI_VERSION 14
 
 /* error codes */
 #define MGS_OK 0
@@ -558,6 +558,44 @@ size_t mgs_volume_workspace_bytes(const MgsVolumeArgs* a);
 int mgs_volume_resample_pad_forward(const MgsVolumeArgs* a, float* out, mgs_stream_t stream);
 int mgs_volume_resample_pad_backward(const MgsVolumeArgs* a, const float* g_out, float* const* g_src, void* workspace,
                                      size_t workspace_bytes, mgs_stream_t stream);
+
+/* ---- the rest of a Perceiver transformer block beside the attention and the GEMMs, fused, fp32 (MG/agents/manigaussian_bc/
+ * perceiver_lang_io.py:56-99: PreNorm's nn.LayerNorm; FeedForward's Linear -> GEGLU -> Linear) -- ABI v14 ----
+ * layernorm, rows of D floats (1 <= D <= 1024), x read by row stride x_stride >= D (floats):
+ *   mean = sum x / D;  rstd = 1 / sqrt(sum (x - mean)^2 / D + eps)  (the variance from the centred values, never E[x^2] - E[x]^2);
+ *   y = (x - mean) rstd weight + bias, y [rows, D] contiguous;  stats [rows, 2] = (mean, rstd): all the backward keeps beside x.
+ *   One wave holds a row in registers; one launch.
+ * layernorm backward, xhat = (x - mean) rstd, g [rows, D] read by row stride g_stride (0: one row for all rows, else >= D):
+ *   dx = rstd (g w - mean(g w) - xhat mean(g w xhat)), dx [rows, D] contiguous;   dweight = sum_rows g xhat;   dbias = sum_rows g.
+ *   Two launches: the row kernel writes dx and, per SLAB of consecutive rows, the slab's two column sums to the workspace
+ *   [slabs][2][D]; the column kernel adds the slabs in ascending order.  dweight == NULL and dbias == NULL (frozen parameters):
+ *   no partial sums, no second launch, no workspace needed; one of them NULL: that sum is not written.
+ * bias-GEGLU, h [rows, 2 M] read by row stride h_stride >= 2 M (the first linear's product WITHOUT its bias), bias [2 M] or NULL:
+ *   out[r, j] = (h[r, j] + bias[j]) gelu(h[r, M + j] + bias[M + j]),  gelu(t) = t (1 + erf(t / sqrt 2)) / 2,  out [rows, M] contiguous.
+ * bias-GEGLU backward, g [rows, M] by row stride g_stride (0, or >= M); a and gate recomputed from h and bias:
+ *   dh[:, :M] = g gelu(gate);   dh[:, M:] = g a gelu'(gate),  gelu'(t) = Phi(t) + t phi(t)  (1 and 0 in the tails, never NaN);
+ *   dh [rows, 2 M] contiguous, both halves written in place;   dbias [2 M] = sum_rows dh by the same slab scheme, or NULL: no
+ *   partial sums, no second launch, no workspace.
+ * row_split: the number of slabs, 0: the library's choice, 1..64: forced (a test aid; fewer when there are fewer rows).  dx and dh
+ * do not depend on it.  workspace: 16-byte aligned, at least the size query's bytes for (rows, cols), cols = D for the layernorm and
+ * M for the GEGLU (64 slabs: independent of the split; 0: rows or cols < 1).
+ * Every tensor is read as 16-byte aligned vectors whatever its own alignment and written as 16-byte vectors where the address
+ * allows; inputs need 4-byte alignment only.  MGS_ERR_INVALID_ARG before any launch: D outside 1..1024; rows or M < 1; rows D or
+ * rows 2 M above 2^31 - 1; a row stride below its row; row_split outside 0..64; a NULL pointer other than the optional ones; y, dx,
+ * out, dh or a needed workspace not 16-byte aligned.  MGS_ERR_WORKSPACE: a needed workspace below the query's size.
+ * No atomics; every output element is written once from a sum whose terms and order depend on the indices and the split alone:
+ * bit-identical from run to run.  No host read, no allocation, no state: capturable into a HIP graph. */
+size_t mgs_feedforward_workspace_bytes(int64_t rows, int64_t cols);
+int mgs_layernorm_forward(int64_t rows, int D, const float* x, int64_t x_stride, const float* weight, const float* bias, float eps,
+                          float* y, float* stats, mgs_stream_t stream);
+int mgs_layernorm_backward(int64_t rows, int D, const float* x, int64_t x_stride, const float* weight, const float* stats,
+                           const float* g, int64_t g_stride, float* dx, float* dweight, float* dbias, void* workspace,
+                           size_t workspace_bytes, int row_split, mgs_stream_t stream);
+int mgs_bias_geglu_forward(int64_t rows, int64_t M, const float* h, int64_t h_stride, const float* bias, float* out,
+                           mgs_stream_t stream);
+int mgs_bias_geglu_backward(int64_t rows, int64_t M, const float* h, int64_t h_stride, const float* bias, const float* g,
+                            int64_t g_stride, float* dh, float* dbias, void* workspace, size_t workspace_bytes, int row_split,
+                            mgs_stream_t stream);
 
 /* Per-stage device timing (hipEvents on the caller's stream), enabled with
  * mgs_set_option("profile", 1) (render backward only) or 2 (every stage).  mgs_profile_read waits for the

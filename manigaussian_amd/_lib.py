@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmgsplat.so")
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 c_fp = ctypes.c_void_p  # device pointers travel as integers (tensor.data_ptr())
 c_i32 = ctypes.c_int32
@@ -153,6 +153,14 @@ _EXPORTS = {
     "mgs_volume_workspace_bytes": (c_sz, [ctypes.POINTER(MgsVolumeArgs)]),
     "mgs_volume_resample_pad_forward": (ctypes.c_int, [ctypes.POINTER(MgsVolumeArgs), c_fp, c_fp]),
     "mgs_volume_resample_pad_backward": (ctypes.c_int, [ctypes.POINTER(MgsVolumeArgs), c_fp, ctypes.POINTER(c_fp), c_fp, c_sz, c_fp]),
+    "mgs_feedforward_workspace_bytes": (c_sz, [ctypes.c_int64] * 2),
+    "mgs_layernorm_forward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, c_fp, ctypes.c_int64, c_fp, c_fp, ctypes.c_float,
+                                             c_fp, c_fp, c_fp]),
+    "mgs_layernorm_backward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, c_fp, ctypes.c_int64, c_fp, c_fp, c_fp, ctypes.c_int64,
+                                              c_fp, c_fp, c_fp, c_fp, c_sz, ctypes.c_int, c_fp]),
+    "mgs_bias_geglu_forward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, c_fp, ctypes.c_int64, c_fp, c_fp, c_fp]),
+    "mgs_bias_geglu_backward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, c_fp, ctypes.c_int64, c_fp, c_fp, ctypes.c_int64,
+                                               c_fp, c_fp, c_fp, c_sz, ctypes.c_int, c_fp]),
     "mgs_forward_stats": (ctypes.c_int, [ctypes.POINTER(MgsRasterArgs), c_i32, ctypes.POINTER(ctypes.c_int64),
                                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), c_fp]),
     "mgs_debug_geom_layout": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(c_sz)] * 4),

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 14
+#define MGS_ABI_VERSION 15
 
 /* error codes */
 #define MGS_OK 0
@@ -50,6 +50,7 @@ extern "C" {
                                       that by itself; an asynchronous one reports it here instead of a generic MGS_ERR_HIP) */
 
 #define MGS_MAX_FEATURE_CHANNELS 64
+#define MGS_MAX_VIEWS 16             /* views of a batch; also the most Gaussian sets of a set batch */
 
 typedef void* mgs_stream_t; /* hipStream_t */
 
@@ -159,6 +160,65 @@ size_t mgs_binning_bytes2(int R, int chunk_pool, int W, int H, int F);  /* expli
 size_t mgs_binning_direct_extra(int P, int V, int W, int H);
 int mgs_chunk_pool_max(int R, int W, int H);           /* chunk records of the worst case: every chunk of every 8x8 block */
 size_t mgs_backward_scratch_bytes(int P, int M, int F);
+
+/* ---- the workspace plan (ABI v15): HOW LARGE, decided once for every host binding.  Pure functions of (shape, marks,
+ * head-room, budget, options): no pointer to device memory, no launch, no HIP call, no state -- they run without a device.
+ * WHICH path a call takes (worst case or marks, waiting or not, decline), the marks, the budget's accounting and every
+ * message stay with the caller.  The size queries above remain the primitives; the plan is arithmetic over them.
+ * A FORWARD AND ITS BACKWARD MUST BE GIVEN THE SAME PLAN: the same (binning_capacity, chunk_pool, binning_bytes) carve the
+ * binning workspace in both, and the backward's outputs lie where the gradient plan the forward's bwd_accum was sized from
+ * puts them.  Each returns MGS_OK, or MGS_ERR_INVALID_ARG (and leaves its outputs zero) for a negative dimension, W or H < 1,
+ * V or S > MGS_MAX_VIEWS, S > 0 without V > 0, or a row count (V x P, S x P) that does not fit the ABI's int. */
+typedef struct MgsPlanShape {
+  int32_t P, M, F;         /* Gaussians (per set), SH coefficients, feature channels rendered (0: none)              */
+  int32_t W, H;
+  int32_t V, S;            /* V = 0: a single view, else a batch of V views; S = 0: no set batch, else S Gaussian sets */
+  int32_t colors_precomp;  /* a batch's colours are one per Gaussian (else one per (view, Gaussian))                  */
+} MgsPlanShape;
+
+/* The arena [geom | img | binning] and the worst case (every Gaussian in every tile: capacity P x tiles of all views, its
+ * own chunk pool): it `fits` if the capacity is below 2^30 and its bytes are within budget_bytes. */
+typedef struct MgsArenaPlan {
+  size_t geom_bytes, img_bytes;  /* mgs_[views_]geom_bytes / img_bytes, each rounded up to 256                        */
+  size_t worst_bytes;            /* binning bytes of the worst case (0: its capacity is 2^30 or more)                 */
+  int64_t worst_capacity;
+  int32_t worst_pool;            /* mgs_[views_]chunk_pool_max of it if it fits, else 0                               */
+  int32_t worst_fits;
+} MgsArenaPlan;
+int mgs_plan_arena(const MgsPlanShape* s, int64_t budget_bytes, MgsArenaPlan* out);
+/* Bytes of the binning part for (capacity, chunk_pool; 0: the worst case for the capacity).  with_direct_room: plus
+ * mgs_binning_direct_extra behind it, for a NAMED capacity (MgsRasterArgs.binning_capacity > 0) that is not the worst case
+ * (which covers the keys by itself).  0: bad shape, or a capacity that does not fit the ABI's int. */
+size_t mgs_plan_binning_bytes(const MgsPlanShape* s, int64_t capacity, int64_t chunk_pool, int with_direct_room);
+
+/* (capacity, chunk pool) of a forward that goes by what earlier forwards of its shape needed:
+ *   MGS_SIZE_HEADROOM  no wait: the marks (R instances, `chunks` records) times the two head-room factors (in [1, 1024)), truncated,
+ *                      plus 4096 instances / 64 records
+ *   MGS_SIZE_COUNT     a forward that waits for the preprocess, its retry, a recovery: R (a mark, or the count the device
+ *                      reported) + R / 4 + 4096; R < 0 (nothing known: first call of a shape): 4 x max(V, 1) x P + 4096.
+ *                      Pool 0: the worst case for the capacity -- cannot overflow.  chunks and the factors are ignored. */
+#define MGS_SIZE_HEADROOM 0
+#define MGS_SIZE_COUNT 1
+int mgs_plan_capacity(const MgsPlanShape* s, int how, int64_t R, int64_t chunks, double head_instances, double head_chunks,
+                      int64_t* capacity, int64_t* chunk_pool);
+
+/* Per-call options tuned from the mark R of the shape (instances binned by earlier forwards), in place: seg 2048 -> 4096
+ * above 8192 instances per tile (each key is ranked in half as many segments); bin_mode 2 -> 1 above 24576 per tile (the
+ * segment sort + rank merge spreads a very long list over one workgroup per segment), seg likewise.  A seg other than 2048
+ * was set on purpose and stays.  R <= 0: nothing changes. */
+int mgs_plan_options(const MgsPlanShape* s, int64_t R, MgsOptions* opt);
+
+/* The backward's single allocation, offsets in FLOATS: [scratch | dL_dcolors | dL_dfeature | means3D | opacity | sh | scales
+ * | rotations | cov3D | means2D | pad].  The first three regions are the accumulator block (MgsRasterArgs.bwd_accum,
+ * accum_bytes of it: may reach into the next, fully rewritten, region); the gradients of the Gaussian parameters are
+ * contiguous.  A batch has V x P means2D rows and, unless colors_precomp, V x P colour rows; a set batch S x P rows of
+ * every per-Gaussian gradient. */
+typedef struct MgsGradientPlan {
+  int64_t scratch, colors, feature, means3D, opacity, sh, scales, rotations, cov3D, means2D, pad;
+  int64_t total;       /* floats */
+  size_t accum_bytes;
+} MgsGradientPlan;
+int mgs_plan_gradients(const MgsPlanShape* s, MgsGradientPlan* out);
 
 /* Forward, stage 1: preprocess + tile-count scan (K2, K3 of SURVEY.md 2b).
  * Replaces the first half of Rasterizer::forward (RAST/cuda_rasterizer/rasterizer_impl.cu:198-284).

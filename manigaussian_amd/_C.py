@@ -63,60 +63,10 @@ def _fill_args(a, *, P, D, M, F, W, H, tanfovx, tanfovy, scale_modifier, prefilt
     a.img, a.img_bytes = _ptr(img), 0 if img is None else img.numel()
 
 
-# ---- host-side caches: everything that is a pure function of the problem shape is computed once --------------------------------
-# (V: 0 for a single view, else the views of a batch -- the mgs_views_* size functions)
-_SIZES = {}      # (P, M, W, H, V) -> (geom bytes, img bytes), both rounded up to 256
-_BIN_BYTES = {}  # (cap, pool, W, H, F, V, P) -> binning bytes
-_WORST = {}      # (P, W, H, F, V, safe_bytes) -> (cannot_overflow, cap_worst, pool_worst, worst bytes)
-_LAYOUTS = {}    # (P, M, F, V, per-view colours, S) -> (sizes, accum_bytes)
+# ---- host-side caches: what is a pure function of the problem shape is computed once (sizes: _lib.plan_*, the library's plan) ----
 _TEMPLATES = {}  # shape + settings scalars + options version -> bytes of a pre-filled MgsRasterArgs (V is not in the struct)
 _EMPTY_U8 = {}   # device -> an empty uint8 tensor (placeholder for workspaces that live in another tensor's arena)
 _SPLIT_WORKSPACES = False  # testing: geom / img / binning as three allocations (guard bands behind each, tests/test_gpu_parity.py)
-
-
-def _up256(n):
-    return (n + 255) & ~255
-
-
-def _shape_sizes(L, P, M, W, H, V):
-    k = (P, M, W, H, V)
-    v = _SIZES.get(k)
-    if v is None:
-        g, i = (L.mgs_views_geom_bytes(P, M, W, H, V), L.mgs_views_img_bytes(W, H, V)) if V else \
-            (L.mgs_geom_bytes(P, M, W, H), L.mgs_img_bytes(W, H))
-        v = _SIZES[k] = (_up256(g), _up256(i))
-    return v
-
-
-def _bin_bytes(L, cap, pool, W, H, F, V=0, P=0):
-    """Bytes of the binning workspace; P > 0: plus the room in which the forward preprocess writes the tile keys itself (no bin
-    scatter launch; include/mgsplat.h mgs_binning_direct_extra) where the library offers it for the shape."""
-    k = (cap, pool, W, H, F, V, P)
-    v = _BIN_BYTES.get(k)
-    if v is None:
-        if len(_BIN_BYTES) > 4096:
-            _BIN_BYTES.clear()
-        v = L.mgs_views_binning_bytes2(cap, pool, W, H, F, V) if V else L.mgs_binning_bytes2(cap, pool, W, H, F)
-        if P > 0:
-            extra = L.mgs_binning_direct_extra(P, V, W, H)
-            v = _up256(v) + extra if extra else v
-        _BIN_BYTES[k] = v
-    return v
-
-
-def _worst_case(L, P, W, H, F, V, T, dev=None):
-    """(cannot_overflow, capacity, chunk pool, bytes) of the binning workspace that holds every Gaussian in every tile (T: the
-    tiles of all views).  cannot_overflow: it fits the budget."""
-    budget = _state.safe_bytes(dev)
-    k = (P, W, H, F, V, budget)
-    v = _WORST.get(k)
-    if v is None:
-        cap_worst = P * T
-        nbytes = _bin_bytes(L, cap_worst, 0, W, H, F, V) if cap_worst < (1 << 30) else 0  # (pool 0: the worst case's)
-        ok = 0 < nbytes <= budget
-        pool = 0 if not ok else L.mgs_views_chunk_pool_max(cap_worst, W, H, V) if V else L.mgs_chunk_pool_max(cap_worst, W, H)
-        v = _WORST[k] = (ok, cap_worst, pool, nbytes)
-    return v
 
 
 def _template(P, D, M, F, W, H, tanfovx, tanfovy, scale_modifier, prefiltered, debug, include_feature):
@@ -232,8 +182,8 @@ def recover_forward(handle, radii, dev):
     binning = None
     if not handshake_only:
         R = max(int(p.num_rendered), 0)
-        cap = R + R // 4 + 4096
-        nbytes = _bin_bytes(L, cap, 0, W, H, F, V)
+        cap, _ = _lib.plan_capacity(_lib.SIZE_COUNT, int(a.P), V, R)
+        nbytes = _lib.plan_binning_bytes(int(a.P), F, W, H, V, cap, 0, False)
         binning = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     out_color = handle.outs[0]() if handle.outs and handle.outs[0] is not None else None
     out_feat = handle.outs[1]() if handle.outs and handle.outs[1] is not None else None
@@ -260,42 +210,6 @@ def recover_forward(handle, radii, dev):
     if binning is not None:
         handle.keep = (handle.keep, binning)
     return R2
-
-
-def _grad_layout(L, P, M, F, V, precomp=False, S=0):
-    """Float sizes of the backward's single allocation: [scratch | dL_dcolors | dL_dfeature | means3D | opacity | sh |
-    scales | rotations | cov3D | means2D | pad].  The first three regions are the accumulators; the gradients of the
-    Gaussian PARAMETERS (colours or SH, features, means, opacity, scales, rotations) are contiguous, so one all-reduce
-    over the span they cover (parallel.flat_alias) moves nothing else.  A batch of V views has V x P means2D rows and,
-    unless its colours are precomputed (precomp: one per Gaussian), V x P colour rows.  A batch of S Gaussian sets (S > 0,
-    P per set) has S x P rows of every per-Gaussian gradient."""
-    k = (P, M, F, V, precomp and V > 0, S)
-    v = _LAYOUTS.get(k)
-    if v is None:
-        scratch = L.mgs_sets_backward_scratch_bytes(P, M, F, V, S) if S else \
-            L.mgs_views_backward_scratch_bytes(P, M, F, V) if V else L.mgs_backward_scratch_bytes(P, M, F)
-        scratch_f = (scratch + 3) // 4
-        n = max(V, 1) * P  # (view, Gaussian) pairs
-        G = max(S, 1) * P  # (set, Gaussian) rows
-        ncol = G if precomp else n
-        sizes = [scratch_f, 3 * ncol, F * G, 3 * G, G, 3 * M * G, 3 * G, 4 * G, 6 * G, 3 * n, 4]
-        accum_bytes = ((scratch_f + 3 * ncol + F * G) * 4 + 15) // 16 * 16  # may reach into the next, fully rewritten, region
-        v = _LAYOUTS[k] = (sizes, accum_bytes)
-    return v
-
-
-def _grad_offsets(L, P, M, F, V, precomp=False, S=0):
-    """(float offsets of the regions of _grad_layout, total floats)."""
-    k = (P, M, F, V, precomp and V > 0, S, "offs")
-    v = _LAYOUTS.get(k)
-    if v is None:
-        sizes, _ = _grad_layout(L, P, M, F, V, precomp, S)
-        offs, o = [], 0
-        for n in sizes:
-            offs.append(o)
-            o += n
-        v = _LAYOUTS[k] = (tuple(offs), o)
-    return v
 
 
 def compiled():
@@ -401,8 +315,10 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
         # (the marks key of a batch is parsed by the compiled binding's marks store: csrc/mgs_torch.cpp Key)
         key = ("sets", S, V, P, W, H, F, opts["tight_bins"]) if S else \
             ("views", V, P, W, H, F, opts["tight_bins"]) if V else (P, W, H, F, opts["tight_bins"])
-        T = max(V, 1) * ((W + 15) // 16) * ((H + 15) // 16)  # the tiles binned: those of every view
-        cannot_overflow, cap_worst, pool_worst, worst_bytes = _worst_case(L, P, W, H, F, V, T, dev)
+        # ONE allocation for the three opaque workspaces [geom | img | binning] (each a multiple of 256 bytes), one for the
+        # images; radii and the backward's gradient buffer have lifetimes of their own.  The worst case holds every Gaussian in
+        # every tile of every view; cannot_overflow: it fits the budget ...
+        gb, ib, cannot_overflow, cap_worst, pool_worst, worst_bytes = _lib.plan_arena(P, M, F, W, H, V, _state.safe_bytes(dev))
         # ... charged against what live forwards of this device already hold (a node keeps its workspace until its backward):
         # V forwards before the first backward take the worst case only while the SUM fits, the rest go by their marks
         if cannot_overflow and not blocking and _state.forward_mode() != "async" and \
@@ -416,22 +332,19 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
             raise RuntimeError("capturing a rasterizer forward or a view batch into a HIP graph needs the asynchronous path: "
                                "manigaussian_amd.set_forward_mode('async'), then run this shape eagerly (twice) first so that "
                                "its workspace sizes are known, with debug=False")
-        # ONE allocation for the three opaque workspaces [geom | img | binning] (each a multiple of 256 bytes), one for the
-        # images; radii and the backward's gradient buffer have lifetimes of their own
-        gb, ib = _shape_sizes(L, P, M, W, H, V)
         while True:
             if lazy:
                 cap, pool = guess
             else:  # waiting path: the chunk pool is the worst case for the capacity (cannot overflow)
                 m = st.marks.get(key)
-                cap, pool = (m[0] + m[0] // 4 + 4096 if m else 4 * max(V, 1) * P + 4096), 0
+                cap, pool = _lib.plan_capacity(_lib.SIZE_COUNT, P, V, m[0] if m else -1)
             # The blocking path of a single view leaves binning_capacity at 0: the library then derives the carving from the
             # buffer's BYTE COUNT, which is all a caller of the reference-shaped pair rasterize_gaussians /
             # rasterize_gaussians_backward(R: int, binningBuffer) hands back -- forward and backward agree by construction.  The
             # asynchronous path and a batch name (capacity, pool); the backward reuses this very struct (ForwardHandle.a).
             named = lazy or V > 0
             # (room for the keys of the direct binning where the capacity is named: a worst-case capacity covers them itself)
-            bb = _bin_bytes(L, cap, pool, W, H, F, V, P if named and cap != cap_worst else 0)
+            bb = _lib.plan_binning_bytes(P, F, W, H, V, cap, pool, named and cap != cap_worst)
             try:
                 if _SPLIT_WORKSPACES:
                     ws = [torch.empty((n,), **u8) for n in (gb, ib, bb)]
@@ -464,15 +377,16 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
         a.geom, a.geom_bytes, a.img, a.img_bytes = p_geom, gb, p_img, ib
         a.binning, a.binning_bytes = p_bin, bb
         m_ = st.marks.get(key)
-        if m_ is not None:
-            _lib.auto_seg(a, opts, m_[0], T)
+        tuned = m_ and _lib.plan_options(opts["seg"], opts["bin_mode"], m_[0], W, H, V)  # long per-tile lists: mgs_plan_options
+        if tuned:
+            a.opt.seg, a.opt.bin_mode = tuned
         slot_ptr, a.status_tag = st.take_slot()
         if named:
             a.binning_capacity, a.chunk_pool, a.async_forward = cap, pool, int(lazy)
         grad_buffer = None
         if want_grad_buffer:
-            sizes, accum_bytes = _grad_layout(L, P, M, F, V, colors.numel() != 0, S)
-            grad_buffer = torch.empty((sum(sizes),), dtype=_F32, device=dev)
+            _, total, accum_bytes = _lib.plan_gradients(P, M, F, V, S, colors.numel() != 0)
+            grad_buffer = torch.empty((total,), dtype=_F32, device=dev)
             a.bwd_accum, a.bwd_accum_bytes = grad_buffer.data_ptr(), accum_bytes
         stream = _stream(dev)
         what = "rasterize sets" if S else "rasterize views" if V else "rasterize_gaussians"
@@ -480,8 +394,8 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
         pending = binning2 = None
         while rc == _lib.MGS_NEED_CAPACITY:  # (waiting path) first call for this shape, or the scene grew: bin + render again
             st.learn(key, _binned_now(slot_ptr))  # the marks hold BINNED counts (advisor r4: not the 3-sigma-rect count R)
-            cap = R + R // 4 + 4096  # (R: the reference's 3-sigma-rect count, at least the instances binned)
-            binning2 = torch.empty((_bin_bytes(L, cap, 0, W, H, F, V, P if named else 0),), **u8)
+            cap, _ = _lib.plan_capacity(_lib.SIZE_COUNT, P, V, R)  # (R: the reference's 3-sigma-rect count >= the instances binned)
+            binning2 = torch.empty((_lib.plan_binning_bytes(P, F, W, H, V, cap, 0, named),), **u8)
             a.binning, a.binning_bytes = binning2.data_ptr(), binning2.numel()
             if not V:
                 feat_ptr = out_feat.data_ptr() if include_feature else None
@@ -491,7 +405,9 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
             # the ABI has no render-only entry for a batch: the whole batch (of views or of sets) runs again, with room for R
             a.binning_capacity = cap
             _lib.fill_options(a, opts)
-            _lib.auto_seg(a, opts, st.marks.get(key)[0], T)
+            tuned = _lib.plan_options(opts["seg"], opts["bin_mode"], st.marks.get(key)[0], W, H, V)
+            if tuned:
+                a.opt.seg, a.opt.bin_mode = tuned
             slot_ptr, a.status_tag = st.take_slot()
             rc, R = _launch_forward(L, a, views, sets, radii, out_color, out_feat, slot_ptr, stream)
         else:
@@ -598,7 +514,7 @@ def _backward(background, means3D, radii, colors, language_feature, scales, rota
         # them with a single fill; everything else is fully written by the kernels.  Regions are addressed by offset
         # (no split / view tensors on the way in; one as_strided per gradient on the way out).
         (o_scr, o_col, o_feat, o_m3, o_op, o_sh, o_sc, o_rot, o_cov, o_m2, _o_pad), total = \
-            _grad_offsets(L, P, M, F, V, colors.numel() != 0, S)
+            _lib.plan_gradients(P, M, F, V, S, colors.numel() != 0)[:2]
         prezeroed = grad_buffer is not None and grad_buffer.numel() == total
         flat = grad_buffer if prezeroed else torch.empty((total,), dtype=_F32, device=dev)
         base = flat.data_ptr()

@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmgsplat.so")
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 c_fp = ctypes.c_void_p  # device pointers travel as integers (tensor.data_ptr())
 c_i32 = ctypes.c_int32
@@ -68,6 +68,24 @@ class MgsVolumeArgs(ctypes.Structure):
 
 
 MAX_VIEWS = 16  # views of a batch; also the most Gaussian sets of a set batch
+c_i64 = ctypes.c_int64
+
+
+class MgsPlanShape(ctypes.Structure):
+    _fields_ = [(n, c_i32) for n in ("P", "M", "F", "W", "H", "V", "S", "colors_precomp")]
+
+
+class MgsArenaPlan(ctypes.Structure):
+    _fields_ = [("geom_bytes", c_sz), ("img_bytes", c_sz), ("worst_bytes", c_sz), ("worst_capacity", c_i64),
+                ("worst_pool", c_i32), ("worst_fits", c_i32)]
+
+
+class MgsGradientPlan(ctypes.Structure):
+    _fields_ = [(n, c_i64) for n in ("scratch", "colors", "feature", "means3D", "opacity", "sh", "scales", "rotations", "cov3D",
+                                     "means2D", "pad", "total")] + [("accum_bytes", c_sz)]
+
+
+SIZE_HEADROOM, SIZE_COUNT = 0, 1  # mgs_plan_capacity: marks x head-room | a mark or a reported count (R < 0: none known)
 
 _EXPORTS = {
     # name: (restype, argtypes)
@@ -83,6 +101,12 @@ _EXPORTS = {
     "mgs_binning_bytes2": (c_sz, [ctypes.c_int] * 5),
     "mgs_binning_direct_extra": (c_sz, [ctypes.c_int] * 4),
     "mgs_chunk_pool_max": (ctypes.c_int, [ctypes.c_int] * 3),
+    "mgs_plan_arena": (ctypes.c_int, [ctypes.POINTER(MgsPlanShape), c_i64, ctypes.POINTER(MgsArenaPlan)]),
+    "mgs_plan_binning_bytes": (c_sz, [ctypes.POINTER(MgsPlanShape), c_i64, c_i64, ctypes.c_int]),
+    "mgs_plan_capacity": (ctypes.c_int, [ctypes.POINTER(MgsPlanShape), ctypes.c_int, c_i64, c_i64, ctypes.c_double,
+                                         ctypes.c_double, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    "mgs_plan_options": (ctypes.c_int, [ctypes.POINTER(MgsPlanShape), c_i64, ctypes.POINTER(MgsOptions)]),
+    "mgs_plan_gradients": (ctypes.c_int, [ctypes.POINTER(MgsPlanShape), ctypes.POINTER(MgsGradientPlan)]),
     "mgs_forward_result": (ctypes.c_int, [ctypes.POINTER(MgsRasterArgs), c_fp, ctypes.POINTER(c_i32),
                                           ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),
     "mgs_forward_result_views": (ctypes.c_int, [ctypes.POINTER(MgsRasterArgs), c_i32, c_fp, ctypes.POINTER(c_i32),
@@ -253,24 +277,70 @@ def get_option(key: str) -> int:
     return DEFAULT_OPTIONS[key]
 
 
-LONG_LIST = 8192  # instances per tile above which 4096-key segments pay (each key is ranked in half as many segments)
-VERY_LONG_LIST = 24576  # ... above which the segment sort + rank merge beats the bucket rank (scripts/diag/quick_binmode.py)
+# ---- the workspace plan (include/mgsplat.h "the workspace plan"): how large, asked of the library ONCE per distinct question ----
+_PLANS = {}  # (query, its arguments) -> the library's answer: a warm forward sizes itself without a call into the library
 
 
-def auto_seg(a, opts, mark_R, tiles):
-    """The default segment length (2048) is raised to 4096 for shapes whose tiles hold long lists (BASELINE configs[4]'s shape:
-    14 000 instances per tile = 7 segments of 2048, every key ranked in the six others; sort + merge 115 us instead of 123,
-    profiles/r04_exp_segsort.log): known from the instance count of earlier forwards of the shape.  An explicitly set seg is
-    left alone."""
-    if opts["seg"] == 2048 and mark_R and mark_R > LONG_LIST * tiles:
-        a.opt.seg = 4096
-    # ... and the bucket rank (bin_mode 2: a tile's slice in registers, <= 16 384 keys) hands VERY long lists -- more than 24 576
-    # instances per tile on average, e.g. 2 000 000 Gaussians on a 128 x 128 image -- to the segment sort + rank merge, whose
-    # work is spread over one workgroup per segment (590 against 505 us there; the bucket rank wins at every BASELINE shape)
-    if opts["bin_mode"] == 2 and mark_R and mark_R > VERY_LONG_LIST * tiles:
-        a.opt.bin_mode = 1
-        if opts["seg"] == 2048:
-            a.opt.seg = 4096
+def _planned(query):
+    def ask(*key):
+        k = (query, key)
+        v = _PLANS.get(k, _PLANS)  # (the dict itself stands for "not asked yet": None is an answer)
+        if v is _PLANS:
+            if len(_PLANS) > 4096:  # marks that keep growing: drop the answers keyed by counts, keep the per-shape ones
+                for old in [o for o in _PLANS if o[0] in _BY_COUNT]:
+                    del _PLANS[old]
+                if len(_PLANS) > 2048:
+                    _PLANS.clear()
+            v = _PLANS[k] = query(lib(), *key)
+        return v
+    ask.query = query
+    return ask
+
+
+@_planned
+def plan_arena(L, P, M, F, W, H, V, budget):
+    """(geom bytes, img bytes, the worst case fits the budget, its capacity, chunk pool, binning bytes); V: 0 or a batch's views."""
+    o = MgsArenaPlan()
+    check(L.mgs_plan_arena(MgsPlanShape(P, M, F, W, H, V), budget, o), "mgs_plan_arena")
+    return o.geom_bytes, o.img_bytes, bool(o.worst_fits), o.worst_capacity, o.worst_pool, o.worst_bytes
+
+
+@_planned
+def plan_binning_bytes(L, P, F, W, H, V, capacity, pool, direct_room):
+    """Bytes of the binning workspace (pool 0: the worst case for the capacity); direct_room: plus the room in which the forward
+    preprocess writes the tile keys itself (no bin scatter launch) where the library offers it for the shape."""
+    n = L.mgs_plan_binning_bytes(MgsPlanShape(P, 0, F, W, H, V), capacity, pool, int(direct_room))
+    if not n:
+        raise RuntimeError(f"mgs_plan_binning_bytes: {last_error()}")
+    return n
+
+
+@_planned
+def plan_capacity(L, how, P, V, R, chunks=0, head_instances=1.0, head_chunks=1.0):
+    """(capacity, chunk pool) of a forward sized from earlier ones of its shape: SIZE_HEADROOM or SIZE_COUNT."""
+    cap, pool = c_i64(), c_i64()
+    check(L.mgs_plan_capacity(MgsPlanShape(P, 0, 0, 1, 1, V), how, R, chunks, head_instances, head_chunks, cap, pool),
+          "mgs_plan_capacity")
+    return cap.value, pool.value
+
+
+@_planned
+def plan_options(L, seg, bin_mode, R, W, H, V):
+    """(seg, bin_mode) as the library tunes them for a shape whose forwards binned R instances, or None: as they are."""
+    o = MgsOptions(seg=seg, bin_mode=bin_mode)
+    check(L.mgs_plan_options(MgsPlanShape(0, 0, 0, W, H, V), R, o), "mgs_plan_options")
+    return None if (o.seg, o.bin_mode) == (seg, bin_mode) else (o.seg, o.bin_mode)
+
+
+@_planned
+def plan_gradients(L, P, M, F, V, S, precomp):
+    """(float offsets of the eleven regions of the backward's single allocation, total floats, bytes of its accumulator block)."""
+    o = MgsGradientPlan()
+    check(L.mgs_plan_gradients(MgsPlanShape(P, M, F, 1, 1, V, S, int(bool(precomp))), o), "mgs_plan_gradients")
+    return tuple(getattr(o, n) for n, _ in MgsGradientPlan._fields_[:11]), o.total, o.accum_bytes
+
+
+_BY_COUNT = {plan_binning_bytes.query, plan_capacity.query, plan_options.query}  # keyed by marks / counts beside the shape
 
 
 def fill_options(a, opts=None):

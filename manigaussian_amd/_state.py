@@ -139,8 +139,14 @@ def lazy_allowed(cannot_overflow: bool) -> bool:
 # Head-room of an asynchronous forward's workspace over the high-water marks of its shape: the scene may grow by these
 # factors from one call to the next before a call overflows (and raises, late).  Scenes that differ wildly between calls of
 # one shape (a parity sweep, a data loader mixing scenes) want more, or set_forward_mode("blocking").
-_HEADROOM = {"instances": float(os.environ.get("MGS_HEADROOM_INSTANCES", 1.5)),
-             "chunks": float(os.environ.get("MGS_HEADROOM_CHUNKS", 2.0))}
+def _headroom(v) -> float:
+    if not 1.0 <= float(v) < 1024.0:  # (the range mgs_plan_capacity sizes a workspace for: include/mgsplat.h)
+        raise ValueError("head-room factors are >= 1 (and below 1024)")
+    return float(v)
+
+
+_HEADROOM = {"instances": _headroom(os.environ.get("MGS_HEADROOM_INSTANCES", 1.5)),
+             "chunks": _headroom(os.environ.get("MGS_HEADROOM_CHUNKS", 2.0))}
 
 
 # A shape whose WORST-CASE workspace (every Gaussian in every tile, every chunk of every block visited) stays below this many
@@ -219,9 +225,7 @@ def set_headroom(instances: float = None, chunks: float = None):
     """Factors (>= 1) by which an asynchronous forward's instance list / chunk-record pool exceed the largest count seen."""
     for k, v in (("instances", instances), ("chunks", chunks)):
         if v is not None:
-            if not v >= 1.0:
-                raise ValueError("head-room factors are >= 1")
-            _HEADROOM[k] = float(v)
+            _HEADROOM[k] = _headroom(v)
     _push_config()
 
 
@@ -350,7 +354,7 @@ class DeviceState:
         m = self.marks.get(key)
         if m is None or m[1] is None:
             return None
-        return int(m[0] * _HEADROOM["instances"]) + 4096, int(m[1] * _HEADROOM["chunks"]) + 64
+        return _lib.plan_capacity(_lib.SIZE_HEADROOM, 0, 0, m[0], m[1], _HEADROOM["instances"], _HEADROOM["chunks"])
 
     def learn(self, key, R=None, chunks=None, pool_unknown=False):
         m = list(self.marks.get(key) or (0, None))

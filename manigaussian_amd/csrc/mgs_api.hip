@@ -199,82 +199,17 @@ int mgs_get_option(const char* key) {
   return MGS_ERR_INVALID_ARG;
 }
 
-static int num_tiles(int W, int H) { return ((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE); }
 // the bin scatter keeps its per-tile tables in LDS; larger tile grids (or bin_mode 0) keep them in memory
 static bool lds_tables(const Options& o, int T) { return o.bin_mode >= 1 && T <= LDS_TILES; }
 // ... and the lists are ordered by ONE bucket-rank launch (bin_mode 2) instead of segment sort + rank merge
 static bool bucket_rank(const Options& o, int T) { return o.bin_mode == 2 && T <= LDS_TILES; }
 
-// ---- what a call renders: one view, or a batch of views ----
-// V views of ONE Gaussian set in one call are stacked into an atlas (each padded to whole tile rows), every (view, Gaussian)
-// pair is a "virtual Gaussian" with id = view * P + Gaussian, and the binning and compositing kernels run unchanged on the
-// atlas: V x the workgroups per launch, one set of launches per batch.  Per-Gaussian gradients are summed over the views on
-// the device (atomics for colour/feature rows, registers in the backward preprocess).  A single view is NOT a one-view atlas:
-// its image keeps H rows (workspace sizes and kernel arguments).  Past the entry points' own argument checks, everything takes a Pass.
-// A SET batch (mgs_rasterize_*_sets) is a view batch whose views render different Gaussian sets of one size, stacked [S][Pg][.]:
-// view v reads rows view_set[v] * Pg + i (ViewCam::row, RenderArgs::row), everything keyed by the virtual id is unchanged, and
-// the per-Gaussian gradients are [S][Pg][.], each set's summed over its own views.  A view batch is the set batch with S = 1.
-struct Pass {
-  bool batch;             // the views entry points: cameras per view (use_cam), colours / cov3D per (view, Gaussian)
-  int V, Pg, P;           // views, Gaussians per view, (virtual) Gaussians V * Pg
-  int S;                  // Gaussian sets (1 unless a set batch)
-  int F;                  // feature channels rendered (0: none)
-  int tiles_x, tiles_yv;  // tile grid of one view
-  int T;                  // tiles of the image that is binned (all V views)
-  int Hv, Hp, H;          // view height, rows per view in that image, its rows (what the img workspace is carved for)
-  const MgsView* views;   // batch: the per-view cameras (nullptr in the size queries)
-  const int32_t* view_set;  // set batch: the set of every view (nullptr: every view renders set 0)
-};
-// V = 0: a single view; V >= 1: a batch of V views
-static Pass pass_of(int P, int W, int H, int F, int V, const MgsView* views = nullptr, int S = 1,
-                    const int32_t* view_set = nullptr) {
-  Pass s;
-  s.batch = V > 0; s.V = s.batch ? V : 1; s.Pg = P; s.P = P * s.V; s.F = F;
-  s.S = S > 0 ? S : 1;
-  s.tiles_x = (W + TILE - 1) / TILE; s.tiles_yv = (H + TILE - 1) / TILE; s.T = s.tiles_x * s.tiles_yv * s.V;
-  s.Hv = H; s.Hp = s.batch ? s.tiles_yv * TILE : H; s.H = s.batch ? s.V * s.Hp : H;
-  s.views = views;
-  s.view_set = view_set;
-  return s;
-}
 static Pass pass_of(const MgsRasterArgs* a, int V = 0, const MgsView* views = nullptr, int S = 1,
                     const int32_t* view_set = nullptr) {
   return pass_of(a->P, a->W, a->H, a->include_feature ? a->F : 0, V, views, S, view_set);
 }
 // first row of view v's Gaussian set in the stacked attribute tables
 static int set_row(const Pass& s, int v) { return s.view_set ? s.view_set[v] * s.Pg : 0; }
-static size_t geom_bytes(const Pass& s, int M) { size_t t; carve_geom(nullptr, s.P, M, s.T, s.V, &t); return t; }
-static size_t img_bytes(const Pass& s, int W) { size_t t; carve_img(nullptr, W, s.H, &t); return t; }
-
-size_t mgs_geom_bytes(int P, int M, int W, int H) { return geom_bytes(pass_of(P, W, H, 0, 0), M); }
-size_t mgs_img_bytes(int W, int H) { return img_bytes(pass_of(0, W, H, 0, 0), W); }
-static size_t binning_bytes_T(int R, int pool, int T, int F) {
-  size_t t;
-  carve_binning(nullptr, R, T, F, pool > 0 ? (uint32_t)pool : 0u, nullptr, &t);
-  return t;
-}
-size_t mgs_binning_bytes2(int R, int chunk_pool, int W, int H, int F) { return binning_bytes_T(R, chunk_pool, num_tiles(W, H), F); }
-size_t mgs_binning_bytes(int R, int W, int H, int F) { return binning_bytes_T(R, 0, num_tiles(W, H), F); }
-int mgs_chunk_pool_max(int R, int W, int H) { return (int)chunk_pool_max(R > 0 ? (size_t)R : 1, num_tiles(W, H)); }
-size_t mgs_backward_scratch_bytes(int P, int M, int F) { size_t t; carve_bwd(nullptr, P, M, F, &t); return t; }
-
-static Pass views_shape(int W, int H, int V) { return pass_of(0, W, H, 0, V > 0 ? V : 1); }
-size_t mgs_views_geom_bytes(int P, int M, int W, int H, int V) { return geom_bytes(pass_of(P, W, H, 0, V > 0 ? V : 1), M); }
-size_t mgs_views_img_bytes(int W, int H, int V) { return img_bytes(views_shape(W, H, V), W); }
-size_t mgs_views_binning_bytes(int R, int W, int H, int F, int V) { return binning_bytes_T(R, 0, views_shape(W, H, V).T, F); }
-size_t mgs_views_binning_bytes2(int R, int chunk_pool, int W, int H, int F, int V) {
-  return binning_bytes_T(R, chunk_pool, views_shape(W, H, V).T, F);
-}
-int mgs_views_chunk_pool_max(int R, int W, int H, int V) {
-  return (int)chunk_pool_max(R > 0 ? (size_t)R : 1, views_shape(W, H, V).T);
-}
-size_t mgs_views_backward_scratch_bytes(int P, int M, int F, int V) { return mgs_backward_scratch_bytes(P * (V > 0 ? V : 1), M, F); }
-// (the scratch holds the render backward's sums per (view, Gaussian) pair; the per-set accumulators are the caller's
-//  dL_dcolors / dL_dfeature outputs)
-size_t mgs_sets_backward_scratch_bytes(int P, int M, int F, int V, int S) {
-  (void)S;
-  return mgs_views_backward_scratch_bytes(P, M, F, V);
-}
 
 static const uint64_t kStatusPending = ~0ull;
 
@@ -333,11 +268,6 @@ static uint64_t* direct_region(const MgsRasterArgs* a, const BinShape& bs, const
   if (need <= DIRECT_MAX_KEYS && a->binning_bytes >= off + need * sizeof(uint64_t))
     return reinterpret_cast<uint64_t*>(static_cast<char*>(a->binning) + off);
   return nullptr;
-}
-size_t mgs_binning_direct_extra(int P, int V, int W, int H) {
-  const int v = V > 0 ? V : 1;
-  const size_t need = direct_keys_needed((size_t)(P > 0 ? P : 0) * v, v, num_tiles(W, H) * v);
-  return need && need <= DIRECT_MAX_KEYS ? need * sizeof(uint64_t) + 256 : 0;
 }
 
 // The geom and img workspaces: checked against the shape, carved (the geom view's flag words are the img workspace's).

@@ -218,6 +218,47 @@ inline BwdScratch carve_bwd(void* p, int P, int M, int F, size_t* total) {
   return s;
 }
 
+// ---- what a call renders: one view, or a batch of views ----
+// V views of ONE Gaussian set in one call are stacked into an atlas (each padded to whole tile rows), every (view, Gaussian)
+// pair is a "virtual Gaussian" with id = view * P + Gaussian, and the binning and compositing kernels run unchanged on the
+// atlas: V x the workgroups per launch, one set of launches per batch.  Per-Gaussian gradients are summed over the views on
+// the device (atomics for colour/feature rows, registers in the backward preprocess).  A single view is NOT a one-view atlas:
+// its image keeps H rows (workspace sizes and kernel arguments).  Past the entry points' own argument checks, everything takes a Pass.
+// A SET batch (mgs_rasterize_*_sets) is a view batch whose views render different Gaussian sets of one size, stacked [S][Pg][.]:
+// view v reads rows view_set[v] * Pg + i (ViewCam::row, RenderArgs::row), everything keyed by the virtual id is unchanged, and
+// the per-Gaussian gradients are [S][Pg][.], each set's summed over its own views.  A view batch is the set batch with S = 1.
+struct Pass {
+  bool batch;             // the views entry points: cameras per view (use_cam), colours / cov3D per (view, Gaussian)
+  int V, Pg, P;           // views, Gaussians per view, (virtual) Gaussians V * Pg
+  int S;                  // Gaussian sets (1 unless a set batch)
+  int F;                  // feature channels rendered (0: none)
+  int tiles_x, tiles_yv;  // tile grid of one view
+  int T;                  // tiles of the image that is binned (all V views)
+  int Hv, Hp, H;          // view height, rows per view in that image, its rows (what the img workspace is carved for)
+  const MgsView* views;   // batch: the per-view cameras (nullptr in the size queries)
+  const int32_t* view_set;  // set batch: the set of every view (nullptr: every view renders set 0)
+};
+// V = 0: a single view; V >= 1: a batch of V views
+inline Pass pass_of(int P, int W, int H, int F, int V, const MgsView* views = nullptr, int S = 1,
+                    const int32_t* view_set = nullptr) {
+  Pass s;
+  s.batch = V > 0; s.V = s.batch ? V : 1; s.Pg = P; s.P = P * s.V; s.F = F;
+  s.S = S > 0 ? S : 1;
+  s.tiles_x = (W + TILE - 1) / TILE; s.tiles_yv = (H + TILE - 1) / TILE; s.T = s.tiles_x * s.tiles_yv * s.V;
+  s.Hv = H; s.Hp = s.batch ? s.tiles_yv * TILE : H; s.H = s.batch ? s.V * s.Hp : H;
+  s.views = views;
+  s.view_set = view_set;
+  return s;
+}
+inline int num_tiles(int W, int H) { return ((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE); }
+inline size_t geom_bytes(const Pass& s, int M) { size_t t; carve_geom(nullptr, s.P, M, s.T, s.V, &t); return t; }
+inline size_t img_bytes(const Pass& s, int W) { size_t t; carve_img(nullptr, W, s.H, &t); return t; }
+inline size_t binning_bytes_T(int R, int pool, int T, int F) {
+  size_t t;
+  carve_binning(nullptr, R, T, F, pool > 0 ? (uint32_t)pool : 0u, nullptr, &t);
+  return t;
+}
+
 // ---- per-call options: MgsOptions of include/mgsplat.h with the defaults filled in -------------------------------
 struct Options {
   int tight_bins = 1;      // 1: drop (Gaussian,tile) instances whose alpha>=1/255 footprint misses the tile

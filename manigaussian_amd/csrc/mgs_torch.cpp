@@ -182,12 +182,11 @@ struct DeviceState {
     if (pool_unknown) m.chunks = -1;
     else if (chunks >= 0 && chunks > m.chunks) m.chunks = chunks;
   }
-  bool guess(const Key& k, int64_t* cap, int64_t* pool) {
+  bool guess(const Key& k, const MgsPlanShape& shape, int64_t* cap, int64_t* pool) {
     auto it = marks.find(k);
     if (it == marks.end() || it->second.chunks < 0) return false;
-    *cap = (int64_t)(it->second.R * cfg().head_inst) + 4096;
-    *pool = (int64_t)(it->second.chunks * cfg().head_chunks) + 64;
-    return true;
+    return mgs_plan_capacity(&shape, MGS_SIZE_HEADROOM, it->second.R, it->second.chunks, cfg().head_inst, cfg().head_chunks,
+                             cap, pool) == MGS_OK;
   }
 };
 
@@ -321,31 +320,11 @@ bool is_capturing(hipStream_t s) {
   return cs != hipStreamCaptureStatusNone;
 }
 
-inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 bool supported_F(int64_t F) { return F == 3 || F == 4 || F == 8 || F == 16 || F == 32 || F == 64; }
 
-// Float offsets of the backward's single allocation (manigaussian_amd/_C.py _grad_layout):
-// [scratch | dL_dcolors | dL_dfeature | means3D | opacity | sh | scales | rotations | cov3D | means2D | pad]
-struct GradLayout { int64_t scr, col, feat, m3, op, sh, sc, rot, cov, m2, total; size_t accum_bytes; };
-GradLayout grad_layout(int64_t P, int64_t M, int64_t F) {
-  GradLayout g;
-  const int64_t scratch_f = (int64_t)((mgs_backward_scratch_bytes((int)P, (int)M, (int)F) + 3) / 4);
-  int64_t o = 0;
-  g.scr = o; o += scratch_f;
-  g.col = o; o += 3 * P;
-  g.feat = o; o += F * P;
-  g.m3 = o; o += 3 * P;
-  g.op = o; o += P;
-  g.sh = o; o += 3 * M * P;
-  g.sc = o; o += 3 * P;
-  g.rot = o; o += 4 * P;
-  g.cov = o; o += 6 * P;
-  g.m2 = o; o += 3 * P;
-  o += 4;
-  g.total = o;
-  g.accum_bytes = (size_t)(((scratch_f + 3 * P + F * P) * 4 + 15) / 16 * 16);
-  return g;
+// The single-view shape the library's plan is asked about (include/mgsplat.h "the workspace plan"; F: channels rendered).
+MgsPlanShape plan_shape(int64_t P, int64_t M, int64_t F, int64_t W, int64_t H) {
+  return MgsPlanShape{(int32_t)P, (int32_t)M, (int32_t)F, (int32_t)W, (int32_t)H, 0, 0, 0};
 }
 
 const char* kBackwardTwice =
@@ -396,10 +375,12 @@ void MgsRasterizeBackward::recover(DeviceState& st, hipStream_t stream, bool han
     a.opt.set = 1;
     a.opt.table_init = 1;
   } else {
-    const int64_t R = std::max<int64_t>(pending->num_rendered, 0);
-    const int64_t cap = R + R / 4 + 4096;
-    const int Fl = include_feature ? (int)F : 0;
-    const size_t nbytes = mgs_binning_bytes2((int)cap, 0, (int)W, (int)H, Fl);
+    const MgsPlanShape shape = plan_shape(P, M, include_feature ? F : 0, W, H);
+    int64_t cap = 0, pool = 0;
+    check_rc(mgs_plan_capacity(&shape, MGS_SIZE_COUNT, std::max<int64_t>(pending->num_rendered, 0), 0, 1.0, 1.0, &cap, &pool),
+             "mgs_plan_capacity");
+    const size_t nbytes = mgs_plan_binning_bytes(&shape, cap, 0, 0);
+    if (!nbytes) fail(mgs_last_error());
     binning2 = at::empty({(int64_t)nbytes}, ws.options());
     a.binning = binning2.data_ptr();
     a.binning_bytes = nbytes;
@@ -510,7 +491,9 @@ variable_list MgsRasterizeBackward::apply_locked(variable_list&& grads, std::vec
   clk.lap(SB_UNPACK);
   settle(st, stream, warnings);
   clk.lap(SB_SETTLE);
-  const GradLayout L = grad_layout(P, M, include_feature ? F : 0);
+  const MgsPlanShape shape = plan_shape(P, M, include_feature ? F : 0, W, H);
+  MgsGradientPlan L;
+  check_rc(mgs_plan_gradients(&shape, &L), "mgs_plan_gradients");
   const bool prezeroed = grad_buffer.defined() && grad_buffer.numel() == L.total;
   at::Tensor flat = prezeroed ? grad_buffer : at::empty({L.total}, f32);
   grad_buffer = at::Tensor();  // pre-zeroed for ONE backward; a second one (retain_graph) allocates and fills
@@ -518,10 +501,10 @@ variable_list MgsRasterizeBackward::apply_locked(variable_list&& grads, std::vec
   a.accum_prezeroed = prezeroed ? 1 : 0;
   clk.lap(SB_ALLOC);
   check_rc(mgs_rasterize_backward(&a, num_rendered, radii.data_ptr<int32_t>(), g_color.data_ptr<float>(),
-                                  include_feature ? g_feat.data_ptr<float>() : nullptr, base + L.m2, nullptr, base + L.op,
-                                  base + L.col, include_feature ? base + L.feat : nullptr, base + L.m3, base + L.cov,
-                                  M ? base + L.sh : nullptr, base + L.sc, base + L.rot, base + L.scr,
-                                  (size_t)(L.col - L.scr) * 4, stream),
+                                  include_feature ? g_feat.data_ptr<float>() : nullptr, base + L.means2D, nullptr,
+                                  base + L.opacity, base + L.colors, include_feature ? base + L.feature : nullptr,
+                                  base + L.means3D, base + L.cov3D, M ? base + L.sh : nullptr, base + L.scales,
+                                  base + L.rotations, base + L.scratch, (size_t)(L.colors - L.scratch) * 4, stream),
            "rasterize_gaussians_backward");
   clk.lap(SB_LIBRARY);
   // order of the forward's inputs (reference: __init__.py:151-162): means3D, means2D, sh, colors_precomp, language_feature,
@@ -529,15 +512,15 @@ variable_list MgsRasterizeBackward::apply_locked(variable_list&& grads, std::vec
   auto view = [&](int i, at::IntArrayRef sizes, at::IntArrayRef strides, int64_t off) {
     if (task_should_compute_output(i)) out[i] = flat.as_strided(sizes, strides, off);
   };
-  view(0, {P, 3}, {3, 1}, L.m3);
-  view(1, {P, 3}, {3, 1}, L.m2);
+  view(0, {P, 3}, {3, 1}, L.means3D);
+  view(1, {P, 3}, {3, 1}, L.means2D);
   if (M) view(2, {P, M, 3}, {3 * M, 3, 1}, L.sh);
-  view(3, {P, 3}, {3, 1}, L.col);
-  if (include_feature) view(4, {P, F}, {F, 1}, L.feat);
-  view(5, {P, 1}, {1, 1}, L.op);
-  view(6, {P, 3}, {3, 1}, L.sc);
-  view(7, {P, 4}, {4, 1}, L.rot);
-  view(8, {P, 6}, {6, 1}, L.cov);
+  view(3, {P, 3}, {3, 1}, L.colors);
+  if (include_feature) view(4, {P, F}, {F, 1}, L.feature);
+  view(5, {P, 1}, {1, 1}, L.opacity);
+  view(6, {P, 3}, {3, 1}, L.scales);
+  view(7, {P, 4}, {4, 1}, L.rotations);
+  view(8, {P, 6}, {6, 1}, L.cov3D);
   clk.lap(SB_VIEWS);
   counters().backwards++;
   return out;
@@ -551,8 +534,6 @@ inline bool plain(const at::Tensor& t, const c10::Device& dev) {
   return t.scalar_type() == at::kFloat && t.device() == dev && t.is_contiguous();
 }
 inline const float* fptr(const at::Tensor& t) { return t.numel() == 0 ? nullptr : t.data_ptr<float>(); }
-
-struct WorstCase { int64_t P, W, H, F, budget; bool ok; int64_t cap, pool; };
 
 // GaussianRasterizer.forward -> _RasterizeGaussians.apply (RAST/diff_gaussian_rasterization/__init__.py:21-103), the hot path.
 // Returns None when the call is not one this binding handles; the caller then takes manigaussian_amd/_C.py.
@@ -616,30 +597,31 @@ py::object rasterize(const at::Tensor& means3D, const at::Tensor& means2D, const
     safe_bytes = st.auto_safe_bytes;
   }
   const Key key{0, (int32_t)P, (int32_t)W, (int32_t)H, (int32_t)F, opt.tight_bins};
-  const int64_t T = ((W + 15) / 16) * ((H + 15) / 16);
-  // worst case: every Gaussian in every tile, every chunk of every block visited
-  static thread_local WorstCase wc{-1, 0, 0, 0, 0, false, 0, 0};
-  if (!(wc.P == P && wc.W == W && wc.H == H && wc.F == F && wc.budget == safe_bytes)) {
-    const int64_t cap_worst = P * T;
-    const bool ok = cap_worst < ((int64_t)1 << 30) &&
-                    (int64_t)mgs_binning_bytes2((int)cap_worst, 0, (int)W, (int)H, (int)F) <= safe_bytes;
-    wc = WorstCase{P, W, H, F, safe_bytes, ok, cap_worst, ok ? mgs_chunk_pool_max((int)cap_worst, (int)W, (int)H) : 0};
+  // the arena's sizes, and the worst case: every Gaussian in every tile, every chunk of every block visited
+  const MgsPlanShape shape = plan_shape(P, M, F, W, H);
+  struct ArenaMemo { MgsPlanShape shape; int64_t budget; int rc; MgsArenaPlan plan; };  // the library's answer for the last shape
+  static thread_local ArenaMemo memo{{-1, 0, 0, 0, 0, 0, 0, 0}, 0, MGS_ERR_INVALID_ARG, {}};
+  if (std::memcmp(&memo.shape, &shape, sizeof(shape)) != 0 || memo.budget != safe_bytes) {
+    memo.shape = shape; memo.budget = safe_bytes;
+    memo.rc = mgs_plan_arena(&shape, safe_bytes, &memo.plan);
   }
+  if (memo.rc != MGS_OK) return decline();  // (the Python path raises the library's message)
+  const MgsArenaPlan& plan = memo.plan;
   // The worst-case workspace is taken only while the worst cases live forwards of this device still hold, plus this one, stay
   // within the budget (round 5 tested the budget per call: V forwards before the first backward pinned V x 4 GB at
   // configs[2]) -- and only if the allocator can give it; otherwise the shape goes by its marks, like any shape whose
   // worst case does not fit (the reference never allocates more than the count needs, rasterize_points.cu:27-33,84-89).
   const auto u8 = at::TensorOptions().dtype(at::kByte).device(dev);
   const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
-  const size_t gb = up256(mgs_geom_bytes((int)P, (int)M, (int)W, (int)H)), ib = up256(mgs_img_bytes((int)W, (int)H));
+  const size_t gb = plan.geom_bytes, ib = plan.img_bytes;
   const bool want_grad = torch::autograd::compute_requires_grad(means3D, means2D, sh, colors, feat, opacities, scales, rotations, cov3D);
   at::AutoDispatchBelowADInplaceOrView below_autograd;  // plain tensors from here on; the node is attached by hand
   at::Tensor ws;
   std::shared_ptr<Lease> lease;
   size_t bb = 0;
-  bool worst = mode != MODE_ASYNC && wc.ok;
+  bool worst = mode != MODE_ASYNC && plan.worst_fits;
   if (worst) {
-    bb = mgs_binning_bytes2((int)wc.cap, (int)wc.pool, (int)W, (int)H, (int)F);
+    bb = plan.worst_bytes;
     if (st.held_bytes.load() + (int64_t)bb > safe_bytes) {
       worst = false;
     } else {
@@ -657,25 +639,23 @@ py::object rasterize(const at::Tensor& means3D, const at::Tensor& means2D, const
   bool have_guess = worst;
   {
     std::lock_guard<std::mutex> lk(st.mu);
-    if (worst) { cap = wc.cap; pool = wc.pool; }
-    else have_guess = st.guess(key, &cap, &pool);
+    if (worst) { cap = plan.worst_capacity; pool = plan.worst_pool; }
+    else have_guess = st.guess(key, shape, &cap, &pool);
     auto it = st.marks.find(key);
     if (it != st.marks.end()) mark_R = it->second.R;
   }
   const bool lazy = have_guess && (mode == MODE_ASYNC || (mode == MODE_SAFE && worst));
   if (mode == MODE_ASYNC && !lazy) return decline();  // first calls of a shape in async mode: the Python path learns the marks
-  if (!lazy) {  // wait for the preprocess: capacity from the marks, worst-case pool for that capacity (cannot overflow)
-    cap = mark_R ? mark_R + mark_R / 4 + 4096 : 4 * P + 4096;
-    pool = 0;
-  }
-  if (cap >= ((int64_t)1 << 31)) return decline();
+  // wait for the preprocess: capacity from the mark (0: none yet), worst-case pool for that capacity (cannot overflow)
+  if (!lazy) check_rc(mgs_plan_capacity(&shape, MGS_SIZE_COUNT, mark_R ? mark_R : -1, 0, 1.0, 1.0, &cap, &pool), "mgs_plan_capacity");
 
   clk.lap(SG_SIZES);
   // ONE allocation for the three opaque workspaces [geom | img | binning] (each a multiple of 256 bytes)
   if (!worst) {
     // (+ room for the forward preprocess to write the tile keys itself: no bin scatter launch, include/mgsplat.h
     //  mgs_binning_direct_extra; a worst-case capacity, above, covers them by itself)
-    bb = up256(mgs_binning_bytes2((int)cap, (int)pool, (int)W, (int)H, (int)F)) + mgs_binning_direct_extra((int)P, 1, (int)W, (int)H);
+    bb = mgs_plan_binning_bytes(&shape, cap, pool, 1);
+    if (!bb) return decline();  // (a capacity of 2^31 or more, or such a pool: the Python path raises the library's message)
     ws = at::empty({(int64_t)(gb + ib + bb)}, u8);
   }
   at::Tensor out_color, out_feat;
@@ -689,9 +669,9 @@ py::object rasterize(const at::Tensor& means3D, const at::Tensor& means2D, const
   }
   at::Tensor radii = at::empty({P}, at::TensorOptions().dtype(at::kInt).device(dev));
   at::Tensor grad_buffer;
-  GradLayout GL{};
+  MgsGradientPlan GL{};
   if (want_grad) {
-    GL = grad_layout(P, M, F);
+    check_rc(mgs_plan_gradients(&shape, &GL), "mgs_plan_gradients");
     grad_buffer = at::empty({GL.total}, f32);
   }
   clk.lap(SG_ALLOC);
@@ -710,11 +690,7 @@ py::object rasterize(const at::Tensor& means3D, const at::Tensor& means2D, const
   a.binning_capacity = (int32_t)cap; a.chunk_pool = (int32_t)pool;
   a.async_forward = lazy ? 1 : 0;
   a.opt = opt;
-  if (opt.seg == 2048 && mark_R > 8192 * T) a.opt.seg = 4096;  // long per-tile lists (manigaussian_amd/_lib.py auto_seg)
-  if (opt.bin_mode == 2 && mark_R > 24576 * T) {               // very long ones: segment sort + rank merge (same place)
-    a.opt.bin_mode = 1;
-    if (opt.seg == 2048) a.opt.seg = 4096;
-  }
+  (void)mgs_plan_options(&shape, mark_R, &a.opt);  // seg and bin_mode for long per-tile lists
   if (want_grad) {
     a.bwd_accum = grad_buffer.data_ptr();
     a.bwd_accum_bytes = GL.accum_bytes;
@@ -741,8 +717,10 @@ py::object rasterize(const at::Tensor& means3D, const at::Tensor& means2D, const
   at::Tensor binning2;
   if (rc == MGS_NEED_CAPACITY) {  // (waiting path) first call of the shape, or the scene grew: bin + render again with room
     const int64_t binned = (int64_t)(uint32_t)(*(volatile uint64_t*)slot);
-    const int64_t cap2 = (int64_t)nr + nr / 4 + 4096;  // (nr: the reference's 3-sigma-rect count, at least the instances binned)
-    const size_t nb = mgs_binning_bytes2((int)cap2, 0, (int)W, (int)H, (int)F);
+    int64_t cap2 = 0, pool2 = 0;  // (nr: the reference's 3-sigma-rect count, at least the instances binned)
+    check_rc(mgs_plan_capacity(&shape, MGS_SIZE_COUNT, nr, 0, 1.0, 1.0, &cap2, &pool2), "mgs_plan_capacity");
+    const size_t nb = mgs_plan_binning_bytes(&shape, cap2, 0, 0);
+    if (!nb) fail(mgs_last_error());
     binning2 = at::empty({(int64_t)nb}, u8);
     a.binning = binning2.data_ptr(); a.binning_bytes = nb; a.binning_capacity = (int32_t)cap2; a.chunk_pool = 0;
     check_rc(mgs_rasterize_forward_render(&a, nr, radii.data_ptr<int32_t>(), out_color.data_ptr<float>(), feat_ptr, stream),

@@ -105,7 +105,7 @@ with _C.use_compiled(False):
     radii = torch.empty(P, dtype=torch.int32, device=dev)
     nr = ctypes.c_int32(0)
     stream = _C._stream(dev)
-    offs, total = _C._grad_offsets(L, P, 4, F, 0)
+    offs, total, _ = _lib.plan_gradients(P, 4, F, 0, 0, False)
     flat = torch.empty(total, device=dev)
     base = flat.data_ptr()
     (o_scr, o_col, o_feat, o_m3, o_op, o_sh, o_sc, o_rot, o_cov, o_m2, _p) = offs

@@ -1271,11 +1271,9 @@ def test_worst_case_workspace_the_allocator_refuses_falls_back_to_the_marks(V, m
         with _C.use_compiled(False):
             return util.run_hip(sc, cams[0], dC[0], dF[0], 1, True, bg)
 
-    L = _lib.lib()
-    gb, ib = _C._shape_sizes(L, P, 4, W, W, V)
-    ok, cap, pool, _ = _C._worst_case(L, P, W, W, F, V, n * ((W + 15) // 16) ** 2, dev)
+    gb, ib, ok, cap, pool, _ = _lib.plan_arena(P, 4, F, W, W, V, _state.safe_bytes(dev))
     assert ok, "the shape's worst case must fit the budget"
-    refusing = _RefusingTorch(gb + ib + _C._bin_bytes(L, cap, pool, W, W, F, V))
+    refusing = _RefusingTorch(gb + ib + _lib.plan_binning_bytes(P, F, W, W, V, cap, pool, False))
     old_mode = _state.set_forward_mode("blocking")
     try:
         ref = run()

@@ -72,11 +72,13 @@ def test_set_batch_shapes_reach_the_library_per_set():
     assert _C._sh_coeffs(torch.zeros(2, 16384, 4, 3), 2) == 4
     assert _C._sh_coeffs(torch.zeros(16384, 16, 3), 0) == 16
     assert _C._sh_coeffs(torch.zeros(0), 2) == 0
-    L = _lib.lib()
-    sizes, accum = _C._grad_layout(L, 1000, 4, 8, 3, False, 2)
+    def sizes_of(P, M, F, V, S, precomp):  # the regions of the backward's allocation, from the plan's offsets
+        offs, total, _ = _lib.plan_gradients(P, M, F, V, S, precomp)
+        return [b - a for a, b in zip(offs, offs[1:] + (total,))]
+    sizes = sizes_of(1000, 4, 8, 3, 2, False)
     assert sizes[1:9] == [3 * 3 * 1000, 8 * 2000, 3 * 2000, 2000, 3 * 4 * 2000, 3 * 2000, 4 * 2000, 6 * 2000]
     assert sizes[9] == 3 * 3 * 1000  # means2D: per view
-    sizes_p, _ = _C._grad_layout(L, 1000, 0, 8, 3, True, 2)
+    sizes_p = sizes_of(1000, 0, 8, 3, 2, True)
     assert sizes_p[1] == 3 * 2000  # precomputed colours: per set
 
 

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 15
+#define MGS_ABI_VERSION 16
 
 /* error codes */
 #define MGS_OK 0
@@ -440,6 +440,39 @@ int mgs_render_loss_forward(int V, int F, int W, int H, const float* color, cons
                             float* terms, float* loss, void* workspace, size_t workspace_bytes, mgs_stream_t stream);
 int mgs_render_loss_backward(int V, int F, int W, int H, const float* g_up, const float* unit_color, const float* unit_feature,
                              float* out_color, float* out_feature, mgs_stream_t stream);
+
+/* ---- photometric loss: L1 + L2 + D-SSIM (MG/loss.py:9-13 l1_loss, l2_loss; :25-68 gaussian, create_window, ssim, _ssim;
+ *      conf/method/ManiGaussian_BC.yaml:97-98 lambda_l1, lambda_ssim; MG/neural_rendering.py:299-307) ----
+ * For V views (1 .. 16) of C channels (1 .. 64) of W x H pixels: color [V,C,H,W] is the rasterizer's planar output,
+ * contiguous; target is a constant addressed by ELEMENT strides {view, channel, row, column} (a host array of 4), as the
+ * rendering losses' targets are.  Per view v, with x the rendered image, y the target and N = C H W:
+ *   l1[v]   = sum |x - y| / N                          (d|t|/dt at t == 0 is 0, torch's abs)
+ *   l2[v]   = sum (x - y)^2 / N
+ *   psnr[v] = 20 log10(1 / sqrt(l2[v])), 100 where l2[v] == 0                  (decided on the device)
+ *   ssim[v] = sum m / N,  m = ((2 mx my + C1)(2 sxy + C2)) / ((mx^2 + my^2 + C1)(sx + sy + C2)),  C1 = 0.01^2, C2 = 0.03^2
+ *             mx = G*x, my = G*y, sx = G*x^2 - mx^2, sy = G*y^2 - my^2, sxy = G*xy - mx my
+ *   loss    = 0 + sum_v (w[v][0] l1[v] + w[v][1] l2[v] + w[v][2] (1 - ssim[v])), accumulated in this order
+ * G is loss.py's window: 11 x 11, the outer product of MGS_SSIM_WINDOW with itself, zero padding of 5 (the map has the image's
+ * size), applied separably -- rows, then columns.  MGS_SSIM_WINDOW holds the float32 values of loss.gaussian(11, 1.5) bit for
+ * bit (exp in double, rounded to float32, divided by their float32 sum; 9 significant digits round-trip a float32).
+ * weights [V,3]: weights_host (kernel arguments, frozen into a captured graph) or weights_dev (read by the kernels: a captured
+ * graph follows in-place updates); both NULL: all ones.  A zero weight still reports its term and adds an exactly zero gradient.
+ * Outputs: terms [V,4] = (l1, l2, ssim, psnr); *loss; unit_grad [V,C,H,W] = d loss / d color (NULL: not wanted; the gradient
+ * launch and the three per-pixel maps d m / d mx, d m / d sx, d m / d sxy it convolves are then skipped).
+ * workspace: mgs_photometric_workspace_bytes(V, C, W, H) bytes, 16-byte aligned (the three maps and one row of partial sums
+ * per workgroup).  3 launches (2 without unit_grad), no atomics, no host synchronisation: bit-identical from run to run.
+ * mgs_photometric_backward: out[v] = g_up[v * g_up_stride] x unit_grad[v] in one launch; g_up is device memory, g_up_stride
+ * 0 (one scalar for every view: d / d loss) or 1 (one value per view: d / d ssim[v], with weights (0, 0, -1)). */
+#define MGS_SSIM_WINDOW_SIZE 11
+#define MGS_SSIM_WINDOW { 0.00102838012f, 0.00759875821f, 0.0360007733f, 0.109360687f, 0.213005528f, 0.266011715f, \
+                          0.213005528f, 0.109360687f, 0.0360007733f, 0.00759875821f, 0.00102838012f }
+#define MGS_PHOTOMETRIC_MAX_CHANNELS 64
+size_t mgs_photometric_workspace_bytes(int V, int C, int W, int H);
+int mgs_photometric_forward(int V, int C, int W, int H, const float* color, const float* target, const int64_t* target_strides,
+                            const float* weights_host, const float* weights_dev, float* unit_grad, float* terms, float* loss,
+                            void* workspace, size_t workspace_bytes, mgs_stream_t stream);
+int mgs_photometric_backward(int V, int C, int W, int H, const float* g_up, int g_up_stride, const float* unit_grad, float* out,
+                             mgs_stream_t stream);
 
 /* ---- fused LAMB step over flat moment buffers (MG/helpers/optim/lamb.py:47-111; no bias correction, as there) ----
  * For any number of parameter tensors, fp32, in TWO launches.  Per tensor, with the hyper-parameters of its group:

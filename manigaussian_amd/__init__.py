@@ -9,6 +9,7 @@ from .views import GaussianRasterizerBatch  # noqa: F401
 from .regressor import gaussian_epilogue  # noqa: F401
 from .voxel import point_latent_pe  # noqa: F401
 from .losses import manigaussian_losses, rendering_loss  # noqa: F401
+from .photometric import l1_loss, photometric_loss, ssim  # noqa: F401
 from .optim import FusedLamb  # noqa: F401
 from .voxelizer import VoxelGrid, voxelize_images  # noqa: F401
 from .attention import Attention, fused_attention  # noqa: F401

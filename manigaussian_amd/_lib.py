@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmgsplat.so")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 c_fp = ctypes.c_void_p  # device pointers travel as integers (tensor.data_ptr())
 c_i32 = ctypes.c_int32
@@ -157,6 +157,10 @@ _EXPORTS = {
                                                ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.POINTER(ctypes.c_float),
                                                c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_sz, c_fp]),
     "mgs_render_loss_backward": (ctypes.c_int, [ctypes.c_int] * 4 + [c_fp] * 5 + [c_fp]),
+    "mgs_photometric_workspace_bytes": (c_sz, [ctypes.c_int] * 4),
+    "mgs_photometric_forward": (ctypes.c_int, [ctypes.c_int] * 4 + [c_fp, c_fp, ctypes.POINTER(ctypes.c_int64),
+                                               ctypes.POINTER(ctypes.c_float), c_fp, c_fp, c_fp, c_fp, c_fp, c_sz, c_fp]),
+    "mgs_photometric_backward": (ctypes.c_int, [ctypes.c_int] * 4 + [c_fp, ctypes.c_int, c_fp, c_fp, c_fp]),
     "mgs_lamb_chunk_elems": (ctypes.c_int, []),
     "mgs_lamb_workspace_bytes": (c_sz, [ctypes.c_int64]),
     "mgs_lamb_step": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,

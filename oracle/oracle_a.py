@@ -63,12 +63,26 @@ def _clamp_q2(v, lim, tz):
 
 
 def rasterize(means3D, opacities, settings, shs=None, colors_precomp=None, language_feature=None,
-              scales=None, rotations=None, cov3D_precomp=None, means2D=None, dtype=None):
+              scales=None, rotations=None, cov3D_precomp=None, means2D=None, dtype=None, record=None, pin=None):
     """Differentiable restatement.  Returns (color [3,H,W], feature [F,H,W] or [1], radii [P] int32, aux).
 
     means2D, if given ([P,3], zeros), is the reference's screen-space gradient holder
     (gaussian_renderer/__init__.py:28): its autograd gradient equals dL_dmean2D of backward.cu:581-582
-    (NDC units, 0.5*W / 0.5*H folded in)."""
+    (NDC units, 0.5*W / 0.5*H folded in).
+
+    record / pin (both off by default, and then nothing below differs from a run without them) make a float64 run usable as
+    the TRUTH of a float32 run at sizes where the two would otherwise take different discrete decisions:
+      record = {}   the run writes out its discrete decisions: "depth_key" (the float32 z that enters the sort key),
+                    "valid" and "keep" ({tile: bool [pixels, list length]}: the pairs that pass alpha >= 1/255 and
+                    power <= 0, and those blended before the pixel stops), and "radii" / "rects" (not decisions to pin,
+                    but what a pinned run must reproduce on its own).
+      pin = that dict, or a part of it ("depth_key" alone: another float32 implementation's depths, which differ from
+                    this one's in the last bit on hosts whose matrix product rounds otherwise; "valid" and "keep" go
+                    together).  The run sorts by the given depth keys and blends exactly the given pairs; everything smooth
+                    (alpha, the transmittance products, weights, blends, the final T and all that is upstream) stays in the
+                    run's dtype, and Q1 / Q2 stay as they are.  Radii and tile rectangles are computed, then ASSERTED equal
+                    to the recorded ones: a scene where they differ has a Gaussian on a rounding edge of its footprint and
+                    is to be re-seeded."""
     dt = dtype or means3D.dtype
     cast = lambda t: None if t is None else t.to(dt)
     means3D, opacities = cast(means3D), cast(opacities)
@@ -155,7 +169,18 @@ def rasterize(means3D, opacities, settings, shs=None, colors_precomp=None, langu
 
     # binning: rasterizer_impl.cu:70-111 keys, :306-311 stable sort, :116-138 ranges
     with torch.no_grad():
-        depth_bits = p_view[:, 2].detach().float().contiguous().view(torch.int32).long()
+        depth_key = p_view[:, 2].detach().float().contiguous()
+        if pin is not None:
+            if "radii" in pin:
+                assert torch.equal(radii, pin["radii"]), "pinned run: radii differ from the recorded run's (re-seed the case)"
+                assert torch.equal(torch.stack([rx0, ry0, rx1, ry1], 1)[vis], pin["rects"][vis]), \
+                    "pinned run: tile rectangles differ from the recorded run's (re-seed the case)"
+            if "depth_key" in pin:
+                depth_key = pin["depth_key"].float().contiguous()
+        if record is not None:
+            record.update(depth_key=depth_key.clone(), radii=radii.clone(), rects=torch.stack([rx0, ry0, rx1, ry1], 1),
+                          valid={}, keep={})
+        depth_bits = depth_key.view(torch.int32).long()
         ids, tiles = [], []
         mw = int((rx1 - rx0)[vis].max()) if vis.any() else 0
         mh = int((ry1 - ry0)[vis].max()) if vis.any() else 0
@@ -201,12 +226,20 @@ def rasterize(means3D, opacities, settings, shs=None, colors_precomp=None, langu
         G = torch.exp(torch.clamp_max(power, 0.0))
         a_raw = opacities[L, 0][None] * G
         alpha = a_raw + (torch.clamp_max(a_raw, 0.99) - a_raw).detach()          # Q1
-        valid = (power <= 0) & (alpha >= 1.0 / 255.0)                            # forward.cu:345-352
+        if pin is not None and "valid" in pin:
+            valid = pin["valid"][tile]
+        else:
+            valid = (power <= 0) & (alpha >= 1.0 / 255.0)                        # forward.cu:345-352
         one_m = torch.where(valid, 1.0 - alpha, torch.ones_like(alpha))
         T_after = torch.cumprod(one_m, 1)
         T_before = torch.cat([torch.ones_like(T_after[:, :1]), T_after[:, :-1]], 1)
-        term = valid & (T_before * (1.0 - alpha) < 0.0001)                       # forward.cu:353-360
-        keep = valid & (torch.cumsum(term.to(torch.int32), 1) == 0)
+        if pin is not None and "valid" in pin:
+            keep = pin["keep"][tile]
+        else:
+            term = valid & (T_before * (1.0 - alpha) < 0.0001)                   # forward.cu:353-360
+            keep = valid & (torch.cumsum(term.to(torch.int32), 1) == 0)
+        if record is not None:
+            record["valid"][tile], record["keep"][tile] = valid, keep
         w = torch.where(keep, alpha * T_before, torch.zeros_like(alpha))
         Tf = torch.cumprod(torch.where(keep, 1.0 - alpha, torch.ones_like(alpha)), 1)[:, -1]
         C = w @ rgb[L] + Tf[:, None] * bg[None]                                  # forward.cu:388
@@ -245,10 +278,10 @@ def rasterize(means3D, opacities, settings, shs=None, colors_precomp=None, langu
     return out_c, out_f, radii, aux
 
 
-def forward_backward(inputs: dict, settings, d_color, d_feat=None, dtype=torch.float32):
+def forward_backward(inputs: dict, settings, d_color, d_feat=None, dtype=torch.float32, record=None, pin=None):
     """Run fwd + autograd bwd.  inputs: means3D, opacities, [shs|colors_precomp], [language_feature],
     scales, rotations | cov3D_precomp.  Returns (color, feat, radii, grads, aux); grads keyed like
-    oracle_b.backward (means2D in the reference's NDC units)."""
+    oracle_b.backward (means2D in the reference's NDC units).  record / pin: see rasterize()."""
     leaves = {}
     for k, v in inputs.items():
         if v is None:
@@ -260,7 +293,7 @@ def forward_backward(inputs: dict, settings, d_color, d_feat=None, dtype=torch.f
         leaves["means3D"], leaves["opacities"], settings, shs=leaves.get("shs"),
         colors_precomp=leaves.get("colors_precomp"), language_feature=leaves.get("language_feature"),
         scales=leaves.get("scales"), rotations=leaves.get("rotations"), cov3D_precomp=leaves.get("cov3D_precomp"),
-        means2D=leaves["means2D"], dtype=dtype)
+        means2D=leaves["means2D"], dtype=dtype, record=record, pin=pin)
     loss = (color * d_color.to(dtype)).sum()
     if settings.include_feature and d_feat is not None and feat.numel() > 1:
         loss = loss + (feat * d_feat.to(dtype)).sum()

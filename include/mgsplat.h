@@ -586,6 +586,69 @@ int mgs_attention_backward(const MgsAttentionArgs* a, const float* out, const fl
                            float* dkv, void* workspace, size_t workspace_bytes, mgs_stream_t stream);
 int mgs_attention_dropout_mask(const MgsAttentionArgs* a, uint8_t* keep, mgs_stream_t stream);
 
+/* ---- the agent's SE(3) augmentation without a host read (MG/voxel/augmentation.py:11-377, apply_se3_augmentation and
+ * apply_se3_augmentation_with_camera_pose: the rejection loop, its discretisation and the transform of clouds and camera
+ * poses) -- additive exports, the ABI version stays 16 ----
+ * select, ONE launch of ONE workgroup: for every (attempt a < attempts, sample b < B)
+ *   draw     trans_u in [-1, 1)^3 and integer steps in [-rot_steps[i], rot_steps[i]] (0 where rot_steps[i] == 0): row (a, b)
+ *            of `draws` [attempts,B,6] fp32 (trans_u, then roll, pitch, yaw steps as floats) when draws != NULL, else words of
+ *            Philox4x32-10(counter = (g, a, b, offset & 0xffffffff), key as for the attention dropout), g = 0: three words
+ *            -> (word >> 8) 2^-23 - 1 and one -> roll, g = 1: pitch, yaw; a step is ((word (2 k + 1)) >> 32) - k.
+ *            rng_state: DEVICE {seed, offset}, read by the kernel.  mgs_se3_draws writes exactly that table.
+ *   compose  fp32, as torch runs the reference: G = matrix of the xyzw quaternion gripper_pose[b, 3:7] (divided by its squared
+ *            norm), S = Rx(roll) Ry(pitch) Rz(yaw), angle = float(step) * rot_step_rad, perturbed rotation G S; translation
+ *            t + (max - min of the bounds row) * trans_aug_range * trans_u -- the product and the sum in fp64 rounded once to
+ *            fp32 when trans_f64 != 0 (what type promotion does with the agent's float64 range tensor), else fp32 steps.
+ *   discretise  fp64 on those fp32 results, as numpy and scipy do: voxel index min(floor(float(p - min) / ((max - min) /
+ *            (V + 1e-12) + 1e-12)), V - 1) against bounds row (layer > 0 ? b : 0) -- negative, hence INVALID, only below the
+ *            bounds; above them it is clamped and valid --; rotation -> quaternion (rounded to fp32, normalised, w >= 0) ->
+ *            extrinsic xyz Euler degrees + 180, / rot_resolution, rounded half to even, rot_bins -> 0; the gripper entry is
+ *            action_rot_grip[b, 3].
+ *   retry    0 ("batch", the reference): the first attempt in which EVERY sample is valid is taken for all of them; none:
+ *            every sample is the identity.  1 ("sample"): every sample takes its own first valid attempt, or the identity.
+ * -> out_trans int64 [B,3], out_rot_grip int64 [B,4] (the inputs' values for an identity sample), info int32 [1 + B]: the
+ *    first attempt valid for the whole batch, then the attempt each sample took (-1: none / identity), and in the workspace
+ *    one record per sample: rotation S, pivot = gripper translation, target = clamp(pivot + fp32 shift, min over ALL rows of
+ *    bounds[:, :3], max over all rows of bounds[:, 3:]).  bounds: DEVICE [bounds_rows,6], bounds_rows 1 or B.
+ *    action_trans [B,3] and action_rot_grip [B,4]: int64 when action_i64 != 0, else int32.
+ * apply, ONE launch for all sources: every point p of src[i] -- planar [B,3,n_points[i]], element strides stride_b[i] between
+ *   samples and stride_c[i] between the three planes, points unit-stride -- becomes S^T (p - pivot) + target in dst[i],
+ *   contiguous planar; every pose pose_in[i] [B,4,4] becomes (S^T R, S^T (T - pivot) + target, bottom row copied) in pose_out[i].
+ *   An identity sample's points and poses are copied bit for bit.  No in-place use: dst and pose_out are other memory.
+ * MGS_ERR_INVALID_ARG before any launch: B outside 1 .. MGS_SE3_MAX_BATCH, attempts outside 1 .. MGS_SE3_MAX_ATTEMPTS,
+ * voxel_size < 1, bounds_rows neither 1 nor B, a negative rot_steps, retry not 0 or 1, n_sources or n_poses outside
+ * 0 .. MGS_SE3_MAX_SOURCES, n_points outside 1 .. 2^24, a NULL pointer, neither draws nor rng_state.
+ * MGS_ERR_WORKSPACE: fewer bytes than the workspace-size query names (0 for a B outside the limits).
+ * All results are written with ordinary vector stores; no atomics on memory: the same from run to run.  No host read, no
+ * allocation, no state: both calls are capturable into a HIP graph, and a replay follows in-place updates of rng_state. */
+#define MGS_SE3_MAX_SOURCES 8
+#define MGS_SE3_MAX_BATCH 4096
+#define MGS_SE3_MAX_ATTEMPTS 32
+typedef struct MgsSe3Args {
+  int32_t B, attempts, retry, layer, voxel_size, bounds_rows, rot_bins, trans_f64, action_i64;
+  int32_t rot_steps[3];
+  float rot_step_rad;
+  int32_t n_sources, n_poses, pad_;
+  double rot_resolution;
+  double trans_aug_range[3];
+  const float* gripper_pose; /* [B,7] contiguous: translation, quaternion xyzw */
+  const void* action_trans;
+  const void* action_rot_grip;
+  const float* bounds;
+  const uint64_t* rng_state;
+  const float* draws;
+  const float* src[MGS_SE3_MAX_SOURCES];
+  float* dst[MGS_SE3_MAX_SOURCES];
+  int64_t n_points[MGS_SE3_MAX_SOURCES], stride_b[MGS_SE3_MAX_SOURCES], stride_c[MGS_SE3_MAX_SOURCES];
+  const float* pose_in[MGS_SE3_MAX_SOURCES];
+  float* pose_out[MGS_SE3_MAX_SOURCES];
+} MgsSe3Args;
+size_t mgs_se3_workspace_bytes(int B);
+int mgs_se3_select(const MgsSe3Args* a, int64_t* out_trans, int64_t* out_rot_grip, int32_t* info, void* workspace,
+                   size_t workspace_bytes, mgs_stream_t stream);
+int mgs_se3_apply(const MgsSe3Args* a, const void* workspace, size_t workspace_bytes, mgs_stream_t stream);
+int mgs_se3_draws(const MgsSe3Args* a, float* draws, mgs_stream_t stream);
+
 /* ---- the Perceiver's aggregated features, fused, fp32 (MG/helpers/network_utils.py:927-963, class SpatialSoftmax3D, and the
  * nn.AdaptiveMaxPool3d(1) next to it at MG/agents/manigaussian_bc/perceiver_lang_io.py:384,485,504) -- ABI v12 ----
  * feature [rows, N], N = D H W, contiguous, 16-byte aligned; a row is one (batch, channel), rows = B C, row = b C + c.

@@ -16,6 +16,8 @@ from .attention import Attention, fused_attention  # noqa: F401
 from .spatial_softmax import SpatialSoftmax3D, spatial_softmax3d  # noqa: F401
 from .volume import Conv3DBlock, Conv3DUpsampleBlock, resample_pad  # noqa: F401
 from .feedforward import GEGLU, FeedForward, PreNorm, bias_geglu, layer_norm  # noqa: F401
+from .augmentation import (Se3Augmentation, apply_se3_augmentation,  # noqa: F401
+                           apply_se3_augmentation_with_camera_pose)
 from . import camera  # noqa: F401
 from ._state import (check_status, forward_mode, overflow_policy, set_forward_mode, set_headroom,  # noqa: F401
                      set_overflow_policy, set_safe_workspace)

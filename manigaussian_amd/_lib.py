@@ -67,6 +67,21 @@ class MgsVolumeArgs(ctypes.Structure):
                 ("stride_b", ctypes.c_int64 * VOLUME_MAX_SOURCES), ("stride_c", ctypes.c_int64 * VOLUME_MAX_SOURCES)]
 
 
+SE3_MAX_SOURCES, SE3_MAX_BATCH, SE3_MAX_ATTEMPTS = 8, 4096, 32  # MGS_SE3_MAX_*
+
+
+class MgsSe3Args(ctypes.Structure):
+    _fields_ = [(n, c_i32) for n in ("B", "attempts", "retry", "layer", "voxel_size", "bounds_rows", "rot_bins", "trans_f64",
+                                     "action_i64")] + \
+               [("rot_steps", c_i32 * 3), ("rot_step_rad", ctypes.c_float), ("n_sources", c_i32), ("n_poses", c_i32),
+                ("pad_", c_i32), ("rot_resolution", ctypes.c_double), ("trans_aug_range", ctypes.c_double * 3),
+                ("gripper_pose", c_fp), ("action_trans", c_fp), ("action_rot_grip", c_fp), ("bounds", c_fp), ("rng_state", c_fp),
+                ("draws", c_fp), ("src", c_fp * SE3_MAX_SOURCES), ("dst", c_fp * SE3_MAX_SOURCES),
+                ("n_points", ctypes.c_int64 * SE3_MAX_SOURCES), ("stride_b", ctypes.c_int64 * SE3_MAX_SOURCES),
+                ("stride_c", ctypes.c_int64 * SE3_MAX_SOURCES), ("pose_in", c_fp * SE3_MAX_SOURCES),
+                ("pose_out", c_fp * SE3_MAX_SOURCES)]
+
+
 MAX_VIEWS = 16  # views of a batch; also the most Gaussian sets of a set batch
 c_i64 = ctypes.c_int64
 
@@ -173,6 +188,10 @@ _EXPORTS = {
     "mgs_attention_forward": (ctypes.c_int, [ctypes.POINTER(MgsAttentionArgs), c_fp, c_fp, c_fp]),
     "mgs_attention_backward": (ctypes.c_int, [ctypes.POINTER(MgsAttentionArgs)] + [c_fp] * 6 + [c_sz, c_fp]),
     "mgs_attention_dropout_mask": (ctypes.c_int, [ctypes.POINTER(MgsAttentionArgs), c_fp, c_fp]),
+    "mgs_se3_workspace_bytes": (c_sz, [ctypes.c_int]),
+    "mgs_se3_select": (ctypes.c_int, [ctypes.POINTER(MgsSe3Args), c_fp, c_fp, c_fp, c_fp, c_sz, c_fp]),
+    "mgs_se3_apply": (ctypes.c_int, [ctypes.POINTER(MgsSe3Args), c_fp, c_sz, c_fp]),
+    "mgs_se3_draws": (ctypes.c_int, [ctypes.POINTER(MgsSe3Args), c_fp, c_fp]),
     "mgs_spatial_softmax_workspace_bytes": (c_sz, [ctypes.c_int64] * 2),
     "mgs_spatial_softmax_forward": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int] * 4 + [ctypes.c_float, c_fp, c_fp, ctypes.c_int64,
                                                    c_fp, ctypes.c_int64, c_fp, c_fp, c_sz, ctypes.c_int, c_fp]),

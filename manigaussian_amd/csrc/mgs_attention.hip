@@ -21,6 +21,7 @@
 #include <math.h>
 
 #include "mgs_common.h"
+#include "mgs_device.h"
 
 namespace mgs {
 
@@ -50,32 +51,8 @@ struct AttnK {
   float inv_keep, scale, inv_nk;
 };
 
-// ---- dropout: Philox4x32-10 (Salmon et al. 2011), counter (j >> 2, i, b H + h, offset low), key (seed low, seed high ^ offset
+// ---- dropout: Philox4x32-10 (mgs_device.h), counter (j >> 2, i, b H + h, offset low), key (seed low, seed high ^ offset
 // high); element (b H + h, i, j) takes word j & 3 and is kept iff word >= floor(p 2^32).
-struct Philox { uint32_t k0, k1, c3; };
-
-__device__ __forceinline__ Philox philox_init(const unsigned long long* rng) {
-  const unsigned long long seed = rng[0], off = rng[1];
-  Philox p;
-  p.k0 = (uint32_t)seed;
-  p.k1 = (uint32_t)(seed >> 32) ^ (uint32_t)(off >> 32);
-  p.c3 = (uint32_t)off;
-  return p;
-}
-
-__device__ __forceinline__ uint4 philox4(const Philox& ph, uint32_t j4, uint32_t i, uint32_t bh) {
-  uint32_t c0 = j4, c1 = i, c2 = bh, c3 = ph.c3, k0 = ph.k0, k1 = ph.k1;
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return make_uint4(c0, c1, c2, c3);
-}
-
-__device__ __forceinline__ uint32_t word_of(const uint4& w, int r) { return r == 0 ? w.x : r == 1 ? w.y : r == 2 ? w.z : w.w; }
 
 // ---- tile loads: rows [row0, row0 + 64) of a [*, n_rows, stride] array, 64 floats from column `col`, zero beyond n_rows
 template <int NT>

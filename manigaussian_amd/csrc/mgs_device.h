@@ -228,4 +228,32 @@ __device__ __forceinline__ uint32_t wave_incl_scan_add_u32(uint32_t v) {
   return r;
 }
 
+// ---- the library's counter-based random stream: Philox4x32-10 (Salmon et al. 2011).  rng: DEVICE {seed, offset}; the key is
+// (seed low, seed high ^ offset high) and the offset's low word is counter word 3, so every offset is a stream of its own;
+// counter words 0..2 are the caller's (attention: (j >> 2, i, b H + h); the SE(3) draws: (word group, attempt, sample)).
+struct Philox { uint32_t k0, k1, c3; };
+
+__device__ __forceinline__ Philox philox_init(const unsigned long long* rng) {
+  const unsigned long long seed = rng[0], off = rng[1];
+  Philox p;
+  p.k0 = (uint32_t)seed;
+  p.k1 = (uint32_t)(seed >> 32) ^ (uint32_t)(off >> 32);
+  p.c3 = (uint32_t)off;
+  return p;
+}
+
+__device__ __forceinline__ uint4 philox4(const Philox& ph, uint32_t j4, uint32_t i, uint32_t bh) {
+  uint32_t c0 = j4, c1 = i, c2 = bh, c3 = ph.c3, k0 = ph.k0, k1 = ph.k1;
+#pragma unroll
+  for (int r = 0; r < 10; r++) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return make_uint4(c0, c1, c2, c3);
+}
+
+__device__ __forceinline__ uint32_t word_of(const uint4& w, int r) { return r == 0 ? w.x : r == 1 ? w.y : r == 2 ? w.z : w.w; }
+
 }  // namespace mgs

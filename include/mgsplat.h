@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 16
+#define MGS_ABI_VERSION 17
 
 /* error codes */
 #define MGS_OK 0
@@ -219,6 +219,99 @@ typedef struct MgsGradientPlan {
   size_t accum_bytes;
 } MgsGradientPlan;
 int mgs_plan_gradients(const MgsPlanShape* s, MgsGradientPlan* out);
+
+/* ---- the report ledger (ABI v17): WHO IS OUTSTANDING, WHAT WAS LEARNED, WHAT TO SAY -- the host-side accounting of the
+ * asynchronous forward (mgs_rasterize_forward with async_forward = 1, below), kept once in this library for every host binding
+ * that loads it: a process that drives the rasterizer through two bindings sees one ring, one set of marks, one budget and one
+ * list of outstanding forwards per device, and every overflow / hand-shake message has one wording.  Sizing (the plan, above),
+ * launching, allocation and the autograd node stay with the bindings.  Plain host code: it never calls back into a binding
+ * except through the `sync_fn` of a drain, and calls HIP only for that synchronisation when no `sync_fn` is given.  State is
+ * per device index (0 .. MGS_LEDGER_MAX_DEVICES - 1); each device has one mutex, a leaf lock.  Unless said otherwise a
+ * function returns MGS_OK or MGS_ERR_INVALID_ARG (bad device index / NULL; mgs_last_error()). */
+#define MGS_LEDGER_MAX_DEVICES 64
+#define MGS_LEDGER_SLOT_WORDS 4    /* 64-bit words per status slot: three used (mgs_rasterize_forward host_status), one pad */
+
+#define MGS_MODE_SAFE 0            /* see manigaussian_amd/_state.py for what the modes and policies mean to a caller */
+#define MGS_MODE_ASYNC 1
+#define MGS_MODE_BLOCKING 2
+#define MGS_OVERFLOW_REPAIR 0
+#define MGS_OVERFLOW_RAISE 1
+typedef struct MgsLedgerConfig {
+  int32_t mode;                    /* MGS_MODE_*: read by the bindings, which decide the path of a call                      */
+  int32_t overflow_policy;         /* MGS_OVERFLOW_*: what an overflow that a backward can still repair turns into           */
+  double head_instances, head_chunks;  /* head-room of mgs_marks_guess over the marks, each in [1, 1024)                     */
+  int64_t safe_bytes;              /* budget of worst-case workspaces per device; < 0: the binding's default for the device  */
+} MgsLedgerConfig;
+void mgs_ledger_set_config(const MgsLedgerConfig* c);
+void mgs_ledger_get_config(MgsLedgerConfig* c);
+
+/* The ring of status slots, ONE per device: `words` (nslots x MGS_LEDGER_SLOT_WORDS 64-bit words of pinned, device-mapped host
+ * memory that outlives the process's use of the device, or plain memory in a host test) is adopted if the device has no ring
+ * yet.  Returns the ring in force -- the caller's if it was adopted, NULL if there is none (words = NULL only asks).
+ * mgs_ledger_take_slot hands out slots round-robin with a fresh 16-bit tag, skipping the slots of captured tickets;
+ * MGS_ERR_INVALID_ARG "all status slots are held by captured graphs" when none is free. */
+uint64_t* mgs_ledger_ring(int device, uint64_t* words, int nslots);
+int mgs_ledger_ring_slots(int device);
+int mgs_ledger_take_slot(int device, uint64_t** slot, uint32_t* tag);
+
+/* The high-water marks per (device, shape): instances binned and chunk records used by earlier forwards of the shape.
+ * V = 0: a single view; V >= 1: a batch of V views; S >= 1: a batch of V views of S Gaussian sets.  chunks < 0: unknown (the
+ * pool must be the worst case).  get / erase / guess return 1 (found, erased, a guess) or 0; keys returns how many there are
+ * and writes at most `room` of them.  learn: marks only grow (R, chunks < 0: nothing known of that one); pool_unknown resets
+ * the chunk mark.  guess: none without a chunk mark, else mgs_plan_capacity(MGS_SIZE_HEADROOM) with the configured head-room. */
+typedef struct MgsMarkKey { int32_t V, S, P, W, H, F, tight_bins; } MgsMarkKey;
+int mgs_marks_get(int device, const MgsMarkKey* key, int64_t* R, int64_t* chunks);
+int mgs_marks_set(int device, const MgsMarkKey* key, int64_t R, int64_t chunks);
+int mgs_marks_erase(int device, const MgsMarkKey* key);
+int mgs_marks_keys(int device, MgsMarkKey* out, int room);
+int mgs_marks_learn(int device, const MgsMarkKey* key, int64_t R, int64_t chunks, int pool_unknown);
+int mgs_marks_guess(int device, const MgsMarkKey* key, int64_t* capacity, int64_t* chunk_pool);
+
+/* The budget: bytes of WORST-CASE workspaces that live forwards of the device hold.  hold reserves `bytes` if (what is held +
+ * bytes) <= budget -- added first, checked, rolled back: two callers cannot both take the last room -- and returns 1, else 0
+ * and nothing changed.  Whoever was granted a hold gives it back with unhold. */
+int mgs_ledger_hold(int device, int64_t bytes, int64_t budget);
+void mgs_ledger_unhold(int device, int64_t bytes);
+int64_t mgs_ledger_held(int device);
+
+/* A ticket: one enqueued forward whose report has not been folded into the marks.  The ledger copies `a` AS GIVEN TO THAT RUN
+ * (a caller may rewrite its struct for a re-run) and holds one reference while the ticket is outstanding or captured; the
+ * caller holds the other and gives it up with release.  V: 0, or the views of a batch (mgs_forward_result_views decodes).
+ * RECOVERABLE: a backward will follow and can re-render; CAPTURED: recorded into a HIP graph -- it reports at every replay,
+ * keeps its slot for good and is read by mgs_ledger_check_captured only.
+ * poll never blocks: the code of mgs_forward_result (MGS_PENDING until both words carry the ticket's tag) and the counts that
+ * have arrived (-1 before).  backward_enqueued: the backward has been enqueued on whatever the forward left -- too late to
+ * repair.  superseded: a recovery ran this forward again (under a ticket of its own); this one is accounted at most once more,
+ * as a warning. */
+#define MGS_TICKET_RECOVERABLE 1
+#define MGS_TICKET_CAPTURED 2
+typedef struct MgsTicket MgsTicket;
+typedef struct MgsReport { int32_t rc, num_rendered, chunks_used, ref_rendered; } MgsReport;
+MgsTicket* mgs_ledger_add(int device, const MgsRasterArgs* a, int32_t V, const uint64_t* slot, const MgsMarkKey* key,
+                          int flags);  /* NULL: bad argument */
+int mgs_ledger_poll(MgsTicket* t, MgsReport* report);
+void mgs_ledger_backward_enqueued(MgsTicket* t);
+void mgs_ledger_superseded(MgsTicket* t);
+void mgs_ledger_release(MgsTicket* t);
+int mgs_ledger_outstanding(int device);  /* tickets not accounted yet (captured ones apart) */
+
+/* drain: read every report that has arrived and fold it into the marks.  The device is synchronised -- once, with the
+ * device's mutex NOT held, through sync_fn(ctx), or by hipDeviceSynchronize on `device` if sync_fn is NULL -- only if `wait`,
+ * or if more than half the ring is outstanding; a ticket that was outstanding at the synchronisation and is still pending after
+ * it fails with "finished without reporting its instance count" (tickets added meanwhile are kept).  `out`: the text the
+ * caller must raise (the first one; NULL: none) and the warnings it must issue, in this thread's storage, valid until the
+ * thread's next ledger call.  An overflow that its backward can still repair (RECOVERABLE, backward not enqueued, policy
+ * repair) is a warning; under policy raise, or too late, an error -- once.  check_captured polls the captured tickets anew. */
+typedef struct MgsLedgerOut {
+  const char* error;
+  int32_t n_warnings;
+  const char* const* warnings;
+} MgsLedgerOut;
+int mgs_ledger_drain(int device, int wait, void (*sync_fn)(void*), void* ctx, MgsLedgerOut* out);
+int mgs_ledger_check_captured(int device, MgsLedgerOut* out);
+/* What a backward raises under policy raise when ITS forward's report (rc: MGS_NEED_CAPACITY or MGS_RETRY_TABLE_INIT) was
+ * already accounted by an earlier drain. */
+const char* mgs_ledger_lost_step_message(int rc);
 
 /* Forward, stage 1: preprocess + tile-count scan (K2, K3 of SURVEY.md 2b).
  * Replaces the first half of Rasterizer::forward (RAST/cuda_rasterizer/rasterizer_impl.cu:198-284).

@@ -205,7 +205,7 @@ def recover_forward(handle, radii, dev):
     _lib.check(rc, "rasterizer forward (re-run after a workspace overflow)")
     newp = _state.Pending(a, V, slot_ptr, p.key)
     st.add(newp)  # (the marks learn the binned count from its report)
-    p.recovered = True
+    p.supersede()
     handle.pending, handle.R = newp, R2
     if binning is not None:
         handle.keep = (handle.keep, binning)
@@ -312,7 +312,6 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
         # everything that is a function of the shape alone comes from caches (sizes, the pre-filled argument struct)
         tmpl, opts = _template(P, int(degree), M, F, W, H, float(tan_fovx), float(tan_fovy), float(scale_modifier),
                                bool(prefiltered), bool(debug), include_feature)
-        # (the marks key of a batch is parsed by the compiled binding's marks store: csrc/mgs_torch.cpp Key)
         key = ("sets", S, V, P, W, H, F, opts["tight_bins"]) if S else \
             ("views", V, P, W, H, F, opts["tight_bins"]) if V else (P, W, H, F, opts["tight_bins"])
         # ONE allocation for the three opaque workspaces [geom | img | binning] (each a multiple of 256 bytes), one for the
@@ -321,10 +320,13 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
         gb, ib, cannot_overflow, cap_worst, pool_worst, worst_bytes = _lib.plan_arena(P, M, F, W, H, V, _state.safe_bytes(dev))
         # ... charged against what live forwards of this device already hold (a node keeps its workspace until its backward):
         # V forwards before the first backward take the worst case only while the SUM fits, the rest go by their marks
-        if cannot_overflow and not blocking and _state.forward_mode() != "async" and \
-                not _state.worst_case_fits(st.index, worst_bytes, dev):
-            cannot_overflow = False
-        guess = (cap_worst, pool_worst) if cannot_overflow else st.guess(key)  # worst case: no marks, no warm-up call needed
+        # (the question reserves the bytes; "async" takes the worst case whatever is held, and is charged all the same)
+        charge = None
+        if cannot_overflow and not blocking and _state.lazy_allowed(True):
+            charge = _state.Charge(st.index, worst_bytes, None if _state.forward_mode() == "async" else _state.safe_bytes(dev))
+            cannot_overflow = charge.held
+        mark = st.marks.get(key)  # (the one read of the shape's marks in this call)
+        guess = (cap_worst, pool_worst) if cannot_overflow else st.guess_of(mark)  # worst case: no marks, no warm-up call needed
         # prefiltered=True is a checked promise (the reference traps the device): its violation must surface in this call
         lazy = (guess is not None and not blocking and not debug and not prefiltered and
                 _state.lazy_allowed(cannot_overflow))
@@ -336,8 +338,7 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
             if lazy:
                 cap, pool = guess
             else:  # waiting path: the chunk pool is the worst case for the capacity (cannot overflow)
-                m = st.marks.get(key)
-                cap, pool = _lib.plan_capacity(_lib.SIZE_COUNT, P, V, m[0] if m else -1)
+                cap, pool = _lib.plan_capacity(_lib.SIZE_COUNT, P, V, mark[0] if mark else -1)
             # The blocking path of a single view leaves binning_capacity at 0: the library then derives the carving from the
             # buffer's BYTE COUNT, which is all a caller of the reference-shaped pair rasterize_gaussians /
             # rasterize_gaussians_backward(R: int, binningBuffer) hands back -- forward and backward agree by construction.  The
@@ -359,8 +360,11 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
                     raise
                 # the allocator cannot give the worst case: this forward goes by its marks and waits for the preprocess
                 lazy, cannot_overflow = False, False
-        if lazy and cannot_overflow and want_grad_buffer:
-            _state.hold(st.index, worst_bytes, ws[-1])
+        if charge is not None:
+            if lazy and cannot_overflow and want_grad_buffer:
+                charge.give(ws[-1])  # charged until the backward has freed the workspace
+            else:
+                charge.drop()        # (without a backward the workspace dies with this call)
         if include_feature and not V:
             out = torch.empty((3 + F, H, W), dtype=_F32, device=dev)
             out_color, out_feat = out[:3], out[3:]
@@ -376,8 +380,7 @@ def _forward(background, means3D, colors, language_feature, opacity, scales, rot
         a.viewmatrix, a.projmatrix, a.campos = _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos)
         a.geom, a.geom_bytes, a.img, a.img_bytes = p_geom, gb, p_img, ib
         a.binning, a.binning_bytes = p_bin, bb
-        m_ = st.marks.get(key)
-        tuned = m_ and _lib.plan_options(opts["seg"], opts["bin_mode"], m_[0], W, H, V)  # long per-tile lists: mgs_plan_options
+        tuned = mark and _lib.plan_options(opts["seg"], opts["bin_mode"], mark[0], W, H, V)  # long per-tile lists: mgs_plan_options
         if tuned:
             a.opt.seg, a.opt.bin_mode = tuned
         slot_ptr, a.status_tag = st.take_slot()
@@ -446,19 +449,12 @@ def _settle(handle, radii, dev, count):
     if p.rc in (_lib.MGS_NEED_CAPACITY, _lib.MGS_RETRY_TABLE_INIT) and not p.captured:
         if _state.overflow_policy() == "raise":
             _state.device_state(dev).drain()  # folds the report into the marks and raises ...
-            # ... unless an earlier drain already did:
-            if p.rc == _lib.MGS_RETRY_TABLE_INIT:
-                raise RuntimeError("the preprocess of this backward's asynchronous forward gave up waiting for its zeroed tile "
-                                   "tables and binned nothing: its images are incomplete and the step is lost (overflow policy "
-                                   "'raise')")
-            raise RuntimeError("the asynchronous rasterizer forward of this backward outgrew its workspace (the scene grew past "
-                               "the head-room over earlier calls of its shape): its images are incomplete and the step is "
-                               "lost; the next call of the shape gets a larger workspace (overflow policy 'raise')")
+            raise RuntimeError(_lib.lib().mgs_ledger_lost_step_message(p.rc).decode())  # ... unless an earlier drain already did
         return recover_forward(handle, radii, dev)
     if p.rc not in (_lib.MGS_OK, _lib.MGS_PENDING):
         _state.device_state(dev).drain()
     if p.rc == _lib.MGS_PENDING:
-        p.backward_enqueued = True  # too late to repair: if this forward overflowed, the next drain raises
+        p.enqueue_backward()  # too late to repair: if this forward overflowed, the next drain raises
     return count
 
 

@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmgsplat.so")
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 c_fp = ctypes.c_void_p  # device pointers travel as integers (tensor.data_ptr())
 c_i32 = ctypes.c_int32
@@ -102,6 +102,29 @@ class MgsGradientPlan(ctypes.Structure):
 
 SIZE_HEADROOM, SIZE_COUNT = 0, 1  # mgs_plan_capacity: marks x head-room | a mark or a reported count (R < 0: none known)
 
+
+# ---- the report ledger (include/mgsplat.h "the report ledger") ----
+class MgsLedgerConfig(ctypes.Structure):
+    _fields_ = [("mode", c_i32), ("overflow_policy", c_i32), ("head_instances", ctypes.c_double),
+                ("head_chunks", ctypes.c_double), ("safe_bytes", c_i64)]
+
+
+class MgsMarkKey(ctypes.Structure):
+    _fields_ = [(n, c_i32) for n in ("V", "S", "P", "W", "H", "F", "tight_bins")]
+
+
+class MgsReport(ctypes.Structure):
+    _fields_ = [(n, c_i32) for n in ("rc", "num_rendered", "chunks_used", "ref_rendered")]
+
+
+class MgsLedgerOut(ctypes.Structure):
+    _fields_ = [("error", ctypes.c_char_p), ("n_warnings", c_i32), ("warnings", ctypes.POINTER(ctypes.c_char_p))]
+
+
+LEDGER_SLOT_WORDS = 4
+TICKET_RECOVERABLE, TICKET_CAPTURED = 1, 2
+LEDGER_SYNC_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p)  # mgs_ledger_drain's sync_fn (None: the library synchronises)
+
 _EXPORTS = {
     # name: (restype, argtypes)
     "mgs_abi_version": (ctypes.c_int, []),
@@ -122,6 +145,29 @@ _EXPORTS = {
                                          ctypes.c_double, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "mgs_plan_options": (ctypes.c_int, [ctypes.POINTER(MgsPlanShape), c_i64, ctypes.POINTER(MgsOptions)]),
     "mgs_plan_gradients": (ctypes.c_int, [ctypes.POINTER(MgsPlanShape), ctypes.POINTER(MgsGradientPlan)]),
+    "mgs_ledger_set_config": (None, [ctypes.POINTER(MgsLedgerConfig)]),
+    "mgs_ledger_get_config": (None, [ctypes.POINTER(MgsLedgerConfig)]),
+    "mgs_ledger_ring": (c_fp, [ctypes.c_int, c_fp, ctypes.c_int]),
+    "mgs_ledger_ring_slots": (ctypes.c_int, [ctypes.c_int]),
+    "mgs_ledger_take_slot": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(c_fp), ctypes.POINTER(ctypes.c_uint32)]),
+    "mgs_marks_get": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(MgsMarkKey), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    "mgs_marks_set": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(MgsMarkKey), c_i64, c_i64]),
+    "mgs_marks_erase": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(MgsMarkKey)]),
+    "mgs_marks_keys": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(MgsMarkKey), ctypes.c_int]),
+    "mgs_marks_learn": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(MgsMarkKey), c_i64, c_i64, ctypes.c_int]),
+    "mgs_marks_guess": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(MgsMarkKey), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    "mgs_ledger_hold": (ctypes.c_int, [ctypes.c_int, c_i64, c_i64]),
+    "mgs_ledger_unhold": (None, [ctypes.c_int, c_i64]),
+    "mgs_ledger_held": (c_i64, [ctypes.c_int]),
+    "mgs_ledger_add": (c_fp, [ctypes.c_int, ctypes.POINTER(MgsRasterArgs), c_i32, c_fp, ctypes.POINTER(MgsMarkKey), ctypes.c_int]),
+    "mgs_ledger_poll": (ctypes.c_int, [c_fp, ctypes.POINTER(MgsReport)]),
+    "mgs_ledger_backward_enqueued": (None, [c_fp]),
+    "mgs_ledger_superseded": (None, [c_fp]),
+    "mgs_ledger_release": (None, [c_fp]),
+    "mgs_ledger_outstanding": (ctypes.c_int, [ctypes.c_int]),
+    "mgs_ledger_drain": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, LEDGER_SYNC_FN, c_fp, ctypes.POINTER(MgsLedgerOut)]),
+    "mgs_ledger_check_captured": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(MgsLedgerOut)]),
+    "mgs_ledger_lost_step_message": (ctypes.c_char_p, [ctypes.c_int]),
     "mgs_forward_result": (ctypes.c_int, [ctypes.POINTER(MgsRasterArgs), c_fp, ctypes.POINTER(c_i32),
                                           ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),
     "mgs_forward_result_views": (ctypes.c_int, [ctypes.POINTER(MgsRasterArgs), c_i32, c_fp, ctypes.POINTER(c_i32),

@@ -16,11 +16,15 @@ its binning buffer is sized from that count.  Three forward modes (set_forward_m
                     with a RuntimeWarning, or raises late).
   "blocking"        every forward waits for the count (the reference's behaviour, also for small shapes).
 
-This module owns
+The accounting itself lives in libmgsplat.so (csrc/mgs_ledger.hip, include/mgsplat.h "the report ledger"), one store per
+device for this shim and the compiled binding alike:
 
   * the ring of pinned status slots (one per in-flight forward, tagged so that a stale write is recognisable),
   * the high-water marks per (device, problem shape),
-  * the list of forwards whose report has not been read yet.
+  * the forwards whose report has not been read yet, the budget of worst-case workspaces, every message.
+
+This module holds the switches (mode, policy, head-room, budget: pushed to the ledger), the Python faces of a device's state
+and of a ticket (DeviceState, Pending), and issues what a drain hands back as RuntimeWarning / RuntimeError.
 
 Reports are read lazily and never waited for on the hot path: at the next forward, at a backward, or on
 `check_status()`.  If a scene outgrew its workspace the images (and gradients) of THAT call were incomplete; the first
@@ -35,6 +39,7 @@ import threading
 import warnings
 import weakref
 
+import numpy
 import torch
 
 from . import _lib
@@ -43,7 +48,7 @@ NSLOTS = 1024  # status slots per device (four 64-bit words each, three used); f
 SLOT_WORDS = 4
 SLOT_BYTES = 8 * SLOT_WORDS
 
-# ---- the compiled binding (csrc/mgs_torch.cpp -> _mgs_torch.so): owns the marks and the hot autograd path when present --------
+# ---- the compiled binding (csrc/mgs_torch.cpp -> _mgs_torch.so): the hot autograd path when present ---------------------------
 _EXT = [False]  # False: not looked for yet; None: absent / disabled; else the module
 
 
@@ -67,27 +72,20 @@ def ext():
         if e is not None:
             _push_config()
             _lib.push_options()
-            e.set_python_drain(_drain_python_side)
     return e
 
 
 def _push_config():
-    e = _EXT[0]
-    if e:
-        e.configure({"safe": 0, "async": 1, "blocking": 2}[_MODE], {"repair": 0, "raise": 1}[_OVERFLOW],
-                    _HEADROOM["instances"], _HEADROOM["chunks"], -1 if _SAFE_BYTES is None else _SAFE_BYTES)
+    """The switches below, to the ledger: its messages and mgs_marks_guess go by them, the compiled binding reads them there."""
+    c = _lib.MgsLedgerConfig({"safe": 0, "async": 1, "blocking": 2}[_MODE], {"repair": 0, "raise": 1}[_OVERFLOW],
+                             _HEADROOM["instances"], _HEADROOM["chunks"], -1 if _SAFE_BYTES is None else _SAFE_BYTES)
+    _lib.lib().mgs_ledger_set_config(c)
 
-
-def _drain_python_side(index):
-    """Called by the compiled binding: at its first forward on a device (this side's state -- a pinned allocation -- must
-    exist before anybody captures a HIP graph: capture forbids the allocation) and while this side has unread reports."""
-    device_state(torch.device("cuda", index)).drain(_from_ext=True)
 
 _WORDS = {}  # slot pointer -> (numpy view of its device's status block, index of the slot's first word)
 _MODE = os.environ.get("MGS_FORWARD_MODE", "safe")  # "safe" | "async" | "blocking"
 _STATES = {}
 _LOCK = threading.Lock()
-_TAG = [0]
 
 
 def set_forward_mode(mode: str):
@@ -190,35 +188,50 @@ def safe_bytes(dev=None) -> int:
 
 
 # ---- worst-case workspaces that live forwards still hold: the budget is charged against their SUM per device -----------------
-# (round 5 tested it per call: V forwards before the first backward pinned V x 4 GB at BASELINE configs[2].)  The compiled
-# binding keeps the counter when it is loaded (its own forwards charge it too); else this dict does.
-_HELD = {}
-
-
+# (round 5 tested it per call: V forwards before the first backward pinned V x 4 GB at BASELINE configs[2].)  The ledger keeps
+# the counter: the compiled binding's forwards charge it too.
 def held_bytes(index: int) -> int:
     """Bytes of worst-case workspaces live forwards hold on device `index`."""
-    e = _EXT[0]
-    return int(e.held_bytes(index)) if e else _HELD.get(index, 0)
-
-
-def _hold_add(index, delta):
-    e = _EXT[0]
-    if e:
-        e.hold_add(index, int(delta))
-    else:
-        with _LOCK:
-            _HELD[index] = _HELD.get(index, 0) + int(delta)
-
-
-def hold(index: int, nbytes: int, owner):
-    """Charge `nbytes` against device `index`'s budget until `owner` (the workspace tensor) is freed."""
-    _hold_add(index, nbytes)
-    weakref.finalize(owner, _hold_add, index, -int(nbytes))
+    return int(_lib.lib().mgs_ledger_held(index))
 
 
 def worst_case_fits(index: int, nbytes: int, dev=None) -> bool:
-    """May a forward take a worst-case workspace of `nbytes` now?  (what is held + this one) <= the budget."""
+    """Would a worst-case workspace of `nbytes` fit now?  (what is held + this one) <= the budget.  Only a look: a forward
+    that acts on the answer takes a Charge, which asks and reserves in one step."""
     return held_bytes(index) + int(nbytes) <= safe_bytes(dev)
+
+
+def _unhold(index, nbytes):
+    _lib.lib().mgs_ledger_unhold(index, nbytes)
+
+
+def hold(index: int, nbytes: int, owner):
+    """Charge `nbytes` against device `index`'s budget, whatever is held, until `owner` (the workspace tensor) is freed."""
+    Charge(index, nbytes, None).give(owner)
+
+
+class Charge:
+    """A worst-case workspace of `nbytes` asked of device `index`'s budget (None: not asked, charged whatever is held).
+    `held`: it was granted -- mgs_ledger_hold reserves and checks in one step, so two forwards cannot both take the last
+    room.  The charge ends with this object (also when an exception unwinds its frame) unless give() hands it to the
+    workspace tensor, which then carries it until it is freed."""
+    __slots__ = ("index", "nbytes", "held")
+
+    def __init__(self, index, nbytes, budget):
+        self.index, self.nbytes = index, int(nbytes)
+        self.held = bool(_lib.lib().mgs_ledger_hold(index, self.nbytes, (1 << 63) - 1 if budget is None else int(budget)))
+
+    def give(self, owner):
+        if self.held:
+            self.held = False
+            weakref.finalize(owner, _unhold, self.index, self.nbytes)
+
+    def drop(self):
+        if self.held:
+            self.held = False
+            _unhold(self.index, self.nbytes)
+
+    __del__ = drop
 
 
 def set_headroom(instances: float = None, chunks: float = None):
@@ -229,10 +242,39 @@ def set_headroom(instances: float = None, chunks: float = None):
     _push_config()
 
 
+_KEYS = {}  # marks key (tuple) -> MgsMarkKey
+
+
+def _mark_key(key):
+    """(P, W, H, F, tight_bins), ("views", V, P, W, H, F, tight_bins) or ("sets", S, V, P, W, H, F, tight_bins) as the ledger's
+    key struct."""
+    t = tuple(key)
+    k = _KEYS.get(t)
+    if k is None:
+        if len(t) == 5:
+            V, S, rest = 0, 0, t
+        elif len(t) == 7 and t[0] == "views":
+            V, S, rest = t[1], 0, t[2:]
+        elif len(t) == 8 and t[0] == "sets":
+            V, S, rest = t[2], t[1], t[3:]
+        else:
+            raise KeyError("a marks key is (P, W, H, F, tight_bins), ('views', V, P, W, H, F, tight_bins) or "
+                           "('sets', S, V, P, W, H, F, tight_bins)")
+        if len(_KEYS) > 4096:
+            _KEYS.clear()
+        k = _KEYS[t] = _lib.MgsMarkKey(int(V), int(S), *(int(x) for x in rest))
+    return k
+
+
+def _key_tuple(k):
+    rest = (k.P, k.W, k.H, k.F, k.tight_bins)
+    return rest if k.V == 0 else ("sets", k.S, k.V) + rest if k.S > 0 else ("views", k.V) + rest
+
+
 class Pending:
-    """One forward whose device report has not been read yet."""
+    """One forward whose device report has not been read yet: the Python face of a ledger ticket."""
     __slots__ = ("a", "V", "slot_ptr", "key", "num_rendered", "chunks_used", "ref_rendered", "rc", "captured", "recoverable",
-                 "recovered", "backward_enqueued", "tag", "cap", "pool", "words")
+                 "recovered", "backward_enqueued", "words", "ticket", "_release")
 
     def __init__(self, a, V, slot_ptr, key, captured=False, recoverable=False):
         self.a, self.V, self.slot_ptr, self.key = a, V, slot_ptr, key
@@ -244,208 +286,198 @@ class Pending:
         self.recoverable = recoverable    # a backward will follow and can re-render (manigaussian_amd._C.recover_forward)
         self.recovered = False
         self.backward_enqueued = False    # ... but it has been enqueued on the incomplete state already
-        # `a` is shared with the forward's handle and is rewritten by a recovery: remember what THIS run was given
-        self.tag, self.cap, self.pool = int(a.status_tag), int(a.binning_capacity), int(a.chunk_pool)
+        self.ticket = None                # DeviceState.add: the ledger copies `a` as THIS run was given it
+
+    def __del__(self):
+        if self.ticket:
+            self._release(self.ticket)
 
     def poll(self):
         """Non-blocking read of the status words; returns the library's code (MGS_PENDING until both words arrived)."""
         if self.rc != _lib.MGS_PENDING:
             return self.rc
-        if self.recovered:  # its arguments describe the re-run now; this run's verdict is in
-            return self.rc
         w = self.words
         if w is not None and w[0][w[1]] == -1 and w[0][w[1] + 1] == -1:  # both words still "pending": no call into the library
             return self.rc
-        L = _lib.lib()
-        nr, ch, ref = ctypes.c_int32(-1), ctypes.c_int32(-1), ctypes.c_int32(-1)
-        if self.V:
-            rc = L.mgs_forward_result_views(ctypes.byref(self.a), self.V, self.slot_ptr, ctypes.byref(nr), ctypes.byref(ch),
-                                            ctypes.byref(ref))
-        else:
-            rc = L.mgs_forward_result(ctypes.byref(self.a), self.slot_ptr, ctypes.byref(nr), ctypes.byref(ch), ctypes.byref(ref))
-        if nr.value >= 0:
-            self.num_rendered = nr.value
-        if ch.value >= 0:
-            self.chunks_used = ch.value
-        if ref.value >= 0:
-            self.ref_rendered = ref.value
+        r = _lib.MgsReport()
+        rc = _lib.lib().mgs_ledger_poll(self.ticket, r)
+        if r.num_rendered >= 0:
+            self.num_rendered = r.num_rendered
+        if r.chunks_used >= 0:
+            self.chunks_used = r.chunks_used
+        if r.ref_rendered >= 0:
+            self.ref_rendered = r.ref_rendered
         if rc != _lib.MGS_PENDING:
             self.rc = rc
         return rc
 
+    def supersede(self):
+        """A recovery has run this forward again (under a ticket of its own)."""
+        self.recovered = True
+        _lib.lib().mgs_ledger_superseded(self.ticket)
+
+    def enqueue_backward(self):
+        """Its backward has been enqueued before its report arrived: too late to repair."""
+        self.backward_enqueued = True
+        _lib.lib().mgs_ledger_backward_enqueued(self.ticket)
+
 
 class _Marks(collections.abc.MutableMapping):
-    """The marks of one device when the compiled binding is loaded: ONE store, in the binding, shared by its hot path and by
-    this shim (a shape warmed up through either is known to both).  Values are [instances, chunk records or None] lists,
-    copies -- assign to change one."""
+    """The marks of one device: ONE store, in the ledger, shared by the compiled binding's hot path and by this shim (a shape
+    warmed up through either is known to both).  Values are [instances, chunk records or None] lists, copies -- assign to
+    change one."""
 
-    def __init__(self, e, index):
-        self.e, self.index = e, index
+    def __init__(self, index):
+        self.index = index
 
     def __getitem__(self, key):
-        v = self.e.marks_get(self.index, tuple(key))
+        v = self.get(key)
         if v is None:
             raise KeyError(key)
         return v
 
+    def get(self, key, default=None):  # (the hot path's form: no exception for a new shape)
+        R, chunks = ctypes.c_int64(), ctypes.c_int64()
+        if _lib.lib().mgs_marks_get(self.index, _mark_key(key), R, chunks) != 1:
+            return default
+        return [R.value, None if chunks.value < 0 else chunks.value]
+
+    def __contains__(self, key):
+        return self.get(key) is not None
+
     def __setitem__(self, key, value):
-        self.e.marks_set(self.index, tuple(key), int(value[0]), None if value[1] is None else int(value[1]))
+        _lib.lib().mgs_marks_set(self.index, _mark_key(key), int(value[0]), -1 if value[1] is None else int(value[1]))
 
     def __delitem__(self, key):
-        if not self.e.marks_del(self.index, tuple(key)):
+        if _lib.lib().mgs_marks_erase(self.index, _mark_key(key)) != 1:
             raise KeyError(key)
 
     def __iter__(self):
-        return iter(self.e.marks_keys(self.index))
+        L = _lib.lib()
+        n = L.mgs_marks_keys(self.index, None, 0)
+        keys = (_lib.MgsMarkKey * max(n, 1))()
+        n = min(n, L.mgs_marks_keys(self.index, keys, n))
+        return iter([_key_tuple(keys[i]) for i in range(n)])
 
     def __len__(self):
-        return len(self.e.marks_keys(self.index))
+        return _lib.lib().mgs_marks_keys(self.index, None, 0)
+
+
+def _report(out, stacklevel):
+    """Issue what a drain handed back (the texts live in the calling thread's storage until its next ledger call)."""
+    error = out.error.decode() if out.error else None
+    for text in [out.warnings[i].decode() for i in range(out.n_warnings)]:
+        warnings.warn(text, RuntimeWarning, stacklevel=stacklevel)
+    if error:
+        raise RuntimeError(error)
+
+
+_NO_SYNC_FN = _lib.LEDGER_SYNC_FN()  # NULL: the library synchronises by itself (the ctypes call has released the GIL)
+
+
+_TLS = threading.local()  # .out: this thread's MgsLedgerOut (a drain runs in front of every forward)
+
+
+def _drain(index, wait=False, stacklevel=5):
+    try:
+        out = _TLS.out
+    except AttributeError:
+        out = _TLS.out = _lib.MgsLedgerOut()
+    _lib.lib().mgs_ledger_drain(index, int(wait), _NO_SYNC_FN, None, out)
+    if out.error or out.n_warnings:
+        _report(out, stacklevel)
 
 
 class DeviceState:
+    """The Python face of one device's ledger state."""
+
     def __init__(self, dev):
         self.dev = dev
         self.index = dev.index if dev.index is not None else torch.cuda.current_device()
-        self.status = torch.full((SLOT_WORDS * NSLOTS,), -1, dtype=torch.int64).pin_memory()
-        self.base_ptr = self.status.data_ptr()
-        words = self.status.numpy()
-        for i in range(NSLOTS):
-            _WORDS[self.base_ptr + SLOT_BYTES * i] = (words, SLOT_WORDS * i)
-        self.reserved = set()  # slots held by captured graphs
-        self.next_slot = 0
+        _push_config()
+        L = _lib.lib()
+        ring = L.mgs_ledger_ring(self.index, None, 0)
+        if not ring:  # this binding is the first to touch the device: its pinned block becomes the device's ring
+            self.status = torch.full((SLOT_WORDS * NSLOTS,), -1, dtype=torch.int64).pin_memory()
+            ring = L.mgs_ledger_ring(self.index, self.status.data_ptr(), NSLOTS)
+        self.base_ptr = ring
+        n = L.mgs_ledger_ring_slots(self.index)
+        words = numpy.frombuffer((ctypes.c_int64 * (SLOT_WORDS * n)).from_address(ring), dtype=numpy.int64)
+        for i in range(n):
+            _WORDS[ring + SLOT_BYTES * i] = (words, SLOT_WORDS * i)
         # shape key -> [instances high-water, chunk records high-water or None (unknown: worst case)]
-        e = ext()
-        self.marks = _Marks(e, self.index) if e else {}
-        self.pending = collections.deque()
+        self.marks = _Marks(self.index)
+        self.pending = collections.deque()  # this shim's forwards whose report had not arrived when last looked at
         self.captured = []   # forwards recorded into HIP graphs: their slots stay reserved, check_status() reads them
-        self.deferred = collections.deque(maxlen=64)  # overflowed forwards whose backward will re-render (diagnostics)
-        self.lock = threading.Lock()
+        self.deferred = collections.deque(maxlen=64)  # this shim's forwards that reported an overflow (diagnostics)
+        self.lock = threading.Lock()  # (of `pending`: ctypes calls release the GIL)
 
     def take_slot(self):
         """(pointer to two pinned words, tag) for one forward."""
-        with self.lock:
-            reserved = self.reserved
-            for _ in range(NSLOTS):
-                i = self.next_slot
-                self.next_slot = (i + 1) % NSLOTS
-                ptr = self.base_ptr + SLOT_BYTES * i
-                if not reserved or ptr not in reserved:
-                    break
-            else:
-                raise RuntimeError("all status slots are held by captured graphs")
-            _TAG[0] = tag = (_TAG[0] + 1) & 0xffff  # (unique per in-flight forward of this device is all that is needed)
-        return ptr, tag
+        slot, tag = ctypes.c_void_p(), ctypes.c_uint32()
+        if _lib.lib().mgs_ledger_take_slot(self.index, slot, tag) != _lib.MGS_OK:
+            raise RuntimeError(_lib.last_error())
+        return slot.value, tag.value
 
     def add(self, pending):
-        """Register a forward whose report is outstanding (thread-safe: ctypes calls release the GIL)."""
-        with self.lock:
-            if pending.captured:
-                self.captured.append(pending)
-                self.reserved.add(pending.slot_ptr)
-            else:
+        """Register a forward whose report is outstanding."""
+        L = _lib.lib()
+        flags = (_lib.TICKET_RECOVERABLE if pending.recoverable else 0) | (_lib.TICKET_CAPTURED if pending.captured else 0)
+        pending._release = L.mgs_ledger_release
+        pending.ticket = L.mgs_ledger_add(self.index, pending.a, pending.V, pending.slot_ptr, _mark_key(pending.key), flags)
+        if not pending.ticket:
+            raise RuntimeError(_lib.last_error())
+        if pending.captured:
+            self.captured.append(pending)
+        else:
+            with self.lock:
                 self.pending.append(pending)
-                e = _EXT[0]
-                if e:  # the binding's hot path looks at this side's reports too while some are outstanding
-                    e.set_python_pending(self.index, len(self.pending))
 
     # ---- high-water marks ---------------------------------------------------------------------------------------
     def guess(self, key):
         """(capacity, chunk pool) for an asynchronous forward of this shape, or None if the shape is new."""
-        m = self.marks.get(key)
+        return self.guess_of(self.marks.get(key))
+
+    @staticmethod
+    def guess_of(m):
+        """guess() from marks already read (a forward reads its shape's marks once).  Answered from the shim's cache of
+        the library's plan (_lib.plan_capacity) and its own copy of the head-room, not by mgs_marks_guess: a warm forward
+        makes no sizing call into the library, and a DeviceState over any mapping of marks can be asked."""
         if m is None or m[1] is None:
             return None
         return _lib.plan_capacity(_lib.SIZE_HEADROOM, 0, 0, m[0], m[1], _HEADROOM["instances"], _HEADROOM["chunks"])
 
     def learn(self, key, R=None, chunks=None, pool_unknown=False):
-        m = list(self.marks.get(key) or (0, None))
-        if R is not None and R > m[0]:
-            m[0] = R
-        if pool_unknown:
-            m[1] = None
-        elif chunks is not None and (m[1] is None or chunks > m[1]):
-            m[1] = chunks
-        self.marks[key] = m
+        _lib.lib().mgs_marks_learn(self.marks.index, _mark_key(key), -1 if R is None else int(R),
+                                   -1 if chunks is None else int(chunks), int(pool_unknown))
 
     # ---- reports --------------------------------------------------------------------------------------------------
-    def drain(self, wait=False, _from_ext=False):
-        """Read every report that has arrived (wait=True: all of them, synchronising with the device once if one is still
-        outstanding).  Raises if a forward overflowed its workspace or finished without reporting."""
-        e = _EXT[0]
-        if e and not _from_ext:  # reports of forwards the compiled binding enqueued on this device
-            e.check_status(self.index, wait)
-        if not self.pending:
-            return
-        failed = None
-        synced = False
-        with self.lock:  # the deque is only ever mutated under the lock and in place (add() appends under it too)
-            todo = list(self.pending)
-            self.pending.clear()
-            keep = []
-            for i, p in enumerate(todo):
-                rc = p.poll()
-                if rc == _lib.MGS_PENDING and (wait or (len(todo) - i - 1) + len(keep) >= NSLOTS // 2):
-                    if not synced:  # everything enqueued so far has run after this: a report that is still missing never comes
-                        torch.cuda.synchronize(self.dev)
-                        synced = True
-                    rc = p.poll()
-                    if rc == _lib.MGS_PENDING:
-                        failed = failed or "a rasterizer forward finished without reporting its instance count"
-                        continue
-                if rc == _lib.MGS_PENDING:
-                    keep.append(p)
-                    continue
-                failed = self._account(p, rc) or failed
-            self.pending.extendleft(reversed(keep))  # ahead of anything appended meanwhile (nothing: we hold the lock)
-            if e:
-                e.set_python_pending(self.index, len(self.pending))
-        if failed:
-            raise RuntimeError(failed)
-
-    def _account(self, p, rc):
-        """Fold a finished forward into the marks; returns an error message if it overflowed."""
-        if rc == _lib.MGS_OK:
-            self.learn(p.key, p.num_rendered, p.chunks_used)
-            return None
-        if rc in (_lib.MGS_NEED_CAPACITY, _lib.MGS_RETRY_TABLE_INIT):
-            grew = rc == _lib.MGS_NEED_CAPACITY
-            if grew:
-                over_inst = p.num_rendered > p.cap > 0
-                self.learn(p.key, p.num_rendered if p.num_rendered >= 0 else None, None, pool_unknown=not over_inst)
-                what = (f"{p.num_rendered} (Gaussian, tile) instances > capacity {p.cap}" if over_inst else
-                        f"chunk pool of {p.pool} records")
-                msg = ("an asynchronous rasterizer forward outgrew the workspace sized from earlier calls of the same shape "
-                       f"({what}): the images of THAT call were incomplete.  The marks are raised")
-                hint = ("  For scenes that grow abruptly use manigaussian_amd.set_forward_mode('safe') (the default) or a larger "
-                        "set_headroom().")
-                hint2 = ", or use manigaussian_amd.set_forward_mode('safe') (the default) for scenes that grow abruptly."
-            else:  # nothing to learn: a workgroup of the preprocess launch was held back (include/mgsplat.h MGS_RETRY_TABLE_INIT)
-                msg = ("an asynchronous rasterizer forward's preprocess gave up waiting for its zeroed tile tables (a workgroup of "
-                       "the launch made no progress for about a second) and binned nothing: the images of THAT call were incomplete")
-                hint = "  manigaussian_amd.set_options(table_init=1) removes the hand-shake."
-                hint2 = " (manigaussian_amd.set_options(table_init=1) removes the hand-shake)."
-            if p.recovered or (_OVERFLOW == "repair" and p.recoverable and not p.backward_enqueued and not p.captured):
-                # its backward re-renders first (manigaussian_amd._C.recover_forward): the gradients come from a complete
-                # forward; only what the caller computed from the incomplete images in between cannot be repaired
-                if not p.recovered:
-                    self.deferred.append(p)
-                warnings.warn(msg + "; the call's backward re-renders on the blocking path before it runs, but a loss computed "
-                              "from those images was computed from incomplete images." + hint, RuntimeWarning, stacklevel=4)
-                return None
-            if p.recoverable and not p.backward_enqueued and not p.captured:  # (overflow policy "raise")
-                p.recovered = True  # its backward, if it still comes, raises too (manigaussian_amd._C._settle)
-                return msg + "; the step is lost (overflow policy 'raise'): re-run it" + (hint2 if grew else ".")
-            return msg + " and its gradients were computed on the incomplete state; re-run the step" + hint2
-        return f"rasterizer forward failed: {_lib.last_error()} (code {rc})"
+    def drain(self, wait=False):
+        """Read every report of the device that has arrived, this shim's forwards and the compiled binding's alike (wait=True:
+        all of them, synchronising with the device once if one is still outstanding).  Raises if a forward overflowed its
+        workspace or finished without reporting."""
+        try:
+            _drain(self.index, wait)
+        finally:
+            if self.pending:
+                with self.lock:
+                    for _ in range(len(self.pending)):
+                        p = self.pending.popleft()
+                        rc = p.poll()
+                        if rc == _lib.MGS_PENDING and not wait:
+                            self.pending.append(p)
+                        elif rc in (_lib.MGS_NEED_CAPACITY, _lib.MGS_RETRY_TABLE_INIT):
+                            self.deferred.append(p)
 
     def check_captured(self):
-        bad = None
-        for p in self.captured:
+        out = _lib.MgsLedgerOut()
+        _lib.lib().mgs_ledger_check_captured(self.index, out)
+        error = out.error.decode() if out.error else None  # (the texts live until this thread's next ledger call)
+        for p in self.captured:  # every replay reports anew: refresh what the tools read, then raise
             p.rc = _lib.MGS_PENDING
-            rc = p.poll()
-            if rc not in (_lib.MGS_OK, _lib.MGS_PENDING):
-                bad = self._account(p, rc) or bad
-        if bad:
-            raise RuntimeError(bad)
+            p.poll()
+        if error:
+            raise RuntimeError(error)
 
 
 def device_state(dev) -> DeviceState:
@@ -463,19 +495,16 @@ def check_status(device=None, wait=True):
     """Read the outstanding forward reports of `device` (default: all devices used so far), waiting for them unless
     wait=False, and raise if one of them -- or a forward replayed from a captured HIP graph -- overflowed its workspace.
     A training loop calls this wherever it synchronises anyway (logging a loss, an optimizer step)."""
-    seen = set()
-    for dev, st in list(_STATES.items()):
-        if device is not None and torch.device(device) != dev:
-            continue
-        st.drain(wait=wait)  # (drains the compiled binding's reports of the device too)
-        st.check_captured()
-        seen.add(dev.index)
-    e = _EXT[0]
-    if e:  # devices only the compiled binding has used
-        if device is None:
-            e.check_status(-1, wait)
-        else:
-            d = torch.device(device)
-            idx = d.index if d.index is not None else torch.cuda.current_device()
-            if idx not in seen:
-                e.check_status(idx, wait)
+    L = _lib.lib()
+    if device is None:
+        indices = range(torch.cuda.device_count())
+    else:
+        d = torch.device(device)
+        indices = [d.index if d.index is not None else torch.cuda.current_device()]
+    for i in indices:
+        st = _STATES.get(torch.device("cuda", i))
+        if st is not None:
+            st.drain(wait=wait)
+            st.check_captured()
+        elif L.mgs_ledger_ring(i, None, 0):  # only the compiled binding has used it (it captures nothing)
+            _drain(i, wait)

@@ -6,11 +6,13 @@
 // ctypes (manigaussian_amd/_C.py) at 125-133 us of host time per forward + backward -- as much as the 150 us of GPU work, so
 // ManiGaussian's eager caller (MG/neural_rendering.py:283,324 -> MG/gaussian_renderer/__init__.py:74) was host-bound.  This file
 // is the same job in C++ over the SAME C ABI (include/mgsplat.h; no kernel, no HIP code here): argument marshalling, ONE
-// workspace arena, the pinned status slots, the workspace marks, and a torch::autograd::Node whose backward the autograd engine
-// calls without entering Python.  _C.py stays: it is the raw three-function surface of the reference's `_C` module, the
-// multi-view path, HIP-graph capture, debug / prefiltered calls and the fallback when this module is not built.
+// workspace arena and a torch::autograd::Node whose backward the autograd engine calls without entering Python.  _C.py stays: it
+// is the raw three-function surface of the reference's `_C` module, the multi-view path, HIP-graph capture, debug /
+// prefiltered calls and the fallback when this module is not built.  The status slots, the workspace marks, the outstanding
+// reports, the budget and every message of the protocol are the library's (csrc/mgs_ledger.hip, "the report ledger" of
+// include/mgsplat.h): this file and _C.py ask the same store.
 //
-// Host-side protocol (mirrors manigaussian_amd/_state.py, which documents it at length):
+// Host-side protocol (manigaussian_amd/_state.py documents the modes at length):
 //   mode safe   shapes whose worst-case workspace fits the budget: enqueue and return (cannot overflow).  Every other shape:
 //               workspace from the shape's marks, everything enqueued, then wait for the PREPROCESS's report only (status
 //               words 0 and 2); too small -> bin + render again with room (what RAST/cuda_rasterizer/rasterizer_impl.cu:282-289
@@ -30,11 +32,9 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <deque>
 #include <memory>
 #include <mutex>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/mgsplat.h"
@@ -46,18 +46,13 @@ using torch::autograd::variable_list;
 
 namespace {
 
-constexpr int NSLOTS = 1024;         // status slots per device (four 64-bit words each: three used)
-constexpr int64_t SLOT_WORDS = 4;
-enum Mode { MODE_SAFE = 0, MODE_ASYNC = 1, MODE_BLOCKING = 2 };
-enum Policy { POLICY_REPAIR = 0, POLICY_RAISE = 1 };
+constexpr int NSLOTS = 1024;  // status slots of a ring this binding gives a device (MGS_LEDGER_SLOT_WORDS 64-bit words each)
 
+// What is this binding's alone: the switch, and the per-call options every forward carries.  Mode, overflow policy, head-room
+// and budget are the ledger's configuration (mgs_ledger_get_config).
 struct Config {
   std::atomic<bool> enabled{true};
-  std::atomic<int> mode{MODE_SAFE};
-  std::atomic<int> policy{POLICY_REPAIR};
-  double head_inst = 1.5, head_chunks = 2.0;
-  int64_t safe_bytes = -1;  // < 0: per device, 1/32 of its memory and at least 1 GB (manigaussian_amd/_state.py safe_bytes)
-  MgsOptions opt;       // per-call options every forward carries (manigaussian_amd._lib.DEFAULT_OPTIONS)
+  MgsOptions opt;       // (manigaussian_amd._lib.DEFAULT_OPTIONS)
   std::mutex mu;
 };
 Config& cfg() { static Config c; return c; }
@@ -66,35 +61,6 @@ struct Counters {
   std::atomic<int64_t> forwards{0}, backwards{0}, declined{0}, waited{0}, retried{0}, recovered{0}, budget_fallbacks{0};
 };
 Counters& counters() { static Counters c; return c; }
-
-// shape key of the workspace marks: V = 0 single view (this file and manigaussian_amd/_C.py), V >= 1 a batch of V views
-// (manigaussian_amd/_C.py _forward, key ("views", V, P, W, H, F, tight_bins)); S >= 1 a batch of V views of S Gaussian sets
-// (key ("sets", S, V, P, W, H, F, tight_bins): never the marks of a view batch of the same V and P)
-struct Key {
-  int32_t V, P, W, H, F, tight;
-  int32_t S = 0;
-  bool operator==(const Key& o) const {
-    return V == o.V && P == o.P && W == o.W && H == o.H && F == o.F && tight == o.tight && S == o.S;
-  }
-};
-struct KeyHash {
-  size_t operator()(const Key& k) const {
-    uint64_t h = 0x9e3779b97f4a7c15ull;
-    for (int32_t v : {k.V, k.P, k.W, k.H, k.F, k.tight, k.S}) h = (h ^ (uint64_t)(uint32_t)v) * 0x100000001b3ull + 0x632be59bd9b4e019ull;
-    return (size_t)h;
-  }
-};
-struct Mark { int64_t R = 0; int64_t chunks = -1; };  // chunks < 0: unknown (worst-case pool)
-
-// One forward whose device report has not been folded into the marks yet.
-struct PendingRec {
-  MgsRasterArgs a;           // what THIS run was given (status_tag, binning_capacity, chunk_pool, binning_bytes, shape)
-  uint64_t* slot = nullptr;  // three pinned words
-  Key key{};
-  int32_t num_rendered = -1, chunks_used = -1, ref_rendered = -1;
-  int rc = MGS_PENDING;
-  bool recoverable = false, recovered = false, backward_enqueued = false;
-};
 
 // ---- where the host time of a call goes (diagnostics: set_profile(true), profile_read()) ----
 enum Seg { SG_CHECKS = 0, SG_STREAM, SG_DRAIN, SG_SIZES, SG_ALLOC, SG_ARGS, SG_LIBRARY, SG_NODE, SG_RETURN,
@@ -118,14 +84,6 @@ struct SegClock {
   }
 };
 
-constexpr int MAX_DEVICES = 64;
-std::atomic<int> g_py_pending[MAX_DEVICES];  // per device: forwards the Python shim has registered and not read yet (cross-drain hint)
-py::object* g_py_drain = nullptr;  // manigaussian_amd._state: drains the Python side's reports of a device
-
-const char* kOutgrew = "an asynchronous rasterizer forward outgrew the workspace sized from earlier calls of the same shape";
-const char* kHandshake = "an asynchronous rasterizer forward's preprocess gave up waiting for its zeroed tile tables (a workgroup of "
-                         "the launch made no progress for about a second) and binned nothing";
-
 [[noreturn]] void fail(const std::string& what) { throw std::runtime_error(what); }
 
 void check_rc(int rc, const char* what) {
@@ -144,171 +102,56 @@ void warn_runtime(const std::string& msg) {
   if (PyErr_WarnEx(PyExc_RuntimeWarning, msg.c_str(), 2) < 0) throw py::error_already_set();
 }
 
+// What this binding keeps per device beside the ledger: the pinned block it gave the ledger as the device's ring (if it was the
+// first to touch the device) and the default budget.
 struct DeviceState {
-  int index;
-  at::Tensor status;  // pinned int64 [NSLOTS * SLOT_WORDS]
-  uint64_t* base = nullptr;
-  int next_slot = 0;
-  uint32_t tag = 0x4000;  // (the Python ring counts from 0: tags of the two rings rarely meet -- and never share a slot)
-  std::unordered_map<Key, Mark, KeyHash> marks;
-  std::deque<std::shared_ptr<PendingRec>> pending;
-  std::mutex mu;
-  bool python_side_built = false;  // manigaussian_amd._state.DeviceState of this device exists (see rasterize())
-  int64_t auto_safe_bytes = 0;     // the default worst-case-workspace budget of this device
-  // bytes of WORST-CASE workspaces that live forwards still hold on this device (a node keeps its workspace until its backward
-  // has run or the graph is freed; the ctypes shim adds its own through hold_add): the `safe` budget is charged against this
-  // sum, not per call -- V forwards before the first backward would otherwise pin V x 4 GB at BASELINE configs[2]
-  std::atomic<int64_t> held_bytes{0};
-
-  explicit DeviceState(int idx) : index(idx) {}
-
-  void ensure_ring() {
-    if (base) return;
-    status = at::full({NSLOTS * SLOT_WORDS}, -1, at::TensorOptions().dtype(at::kLong).device(at::kCPU)).pin_memory();
-    base = reinterpret_cast<uint64_t*>(status.data_ptr<int64_t>());
-  }
-  uint64_t* take_slot(uint32_t* tag_out) {  // mu held
-    ensure_ring();
-    uint64_t* p = base + (size_t)next_slot * SLOT_WORDS;
-    next_slot = (next_slot + 1) % NSLOTS;
-    tag = (tag + 1) & 0xffffu;
-    *tag_out = tag;
-    return p;
-  }
-  // ---- marks (mu held) ----
-  void learn(const Key& k, int64_t R, int64_t chunks, bool pool_unknown) {
-    Mark& m = marks[k];
-    if (R >= 0 && R > m.R) m.R = R;
-    if (pool_unknown) m.chunks = -1;
-    else if (chunks >= 0 && chunks > m.chunks) m.chunks = chunks;
-  }
-  bool guess(const Key& k, const MgsPlanShape& shape, int64_t* cap, int64_t* pool) {
-    auto it = marks.find(k);
-    if (it == marks.end() || it->second.chunks < 0) return false;
-    return mgs_plan_capacity(&shape, MGS_SIZE_HEADROOM, it->second.R, it->second.chunks, cfg().head_inst, cfg().head_chunks,
-                             cap, pool) == MGS_OK;
-  }
+  std::once_flag ring_once;
+  at::Tensor status;
+  std::atomic<int64_t> auto_safe_bytes{0};  // the default worst-case-workspace budget: 1/32 of the memory, at least 1 GB
 };
+DeviceState& state(int idx) {
+  static DeviceState states[MGS_LEDGER_MAX_DEVICES];
+  if (idx < 0 || idx >= MGS_LEDGER_MAX_DEVICES) fail("device index " + std::to_string(idx) + " is beyond the report ledger");
+  return states[idx];
+}
+void ensure_ring(int idx) {
+  DeviceState& st = state(idx);
+  std::call_once(st.ring_once, [&] {
+    if (mgs_ledger_ring(idx, nullptr, 0)) return;  // (the ctypes shim was first)
+    at::Tensor t = at::full({NSLOTS * MGS_LEDGER_SLOT_WORDS}, -1, at::TensorOptions().dtype(at::kLong).device(at::kCPU)).pin_memory();
+    uint64_t* words = reinterpret_cast<uint64_t*>(t.data_ptr<int64_t>());
+    if (mgs_ledger_ring(idx, words, NSLOTS) == words) st.status = t;
+  });
+}
 
-// A worst-case workspace charged against its device's budget for as long as somebody holds this object.
+// A worst-case workspace that mgs_ledger_hold granted, charged against its device's budget for as long as somebody holds this.
 struct Lease {
-  DeviceState* st;
+  int device;
   int64_t bytes;
-  Lease(DeviceState* s, int64_t b) : st(s), bytes(b) { st->held_bytes += b; }
-  ~Lease() { st->held_bytes -= bytes; }
+  Lease(int d, int64_t b) : device(d), bytes(b) {}
+  ~Lease() { mgs_ledger_unhold(device, bytes); }
   Lease(const Lease&) = delete;
   Lease& operator=(const Lease&) = delete;
 };
 
-std::mutex g_states_mu;
-std::vector<std::unique_ptr<DeviceState>> g_states;
-DeviceState& state(int idx) {
-  std::lock_guard<std::mutex> lk(g_states_mu);
-  if ((int)g_states.size() <= idx) g_states.resize(idx + 1);
-  if (!g_states[idx]) g_states[idx] = std::make_unique<DeviceState>(idx);
-  return *g_states[idx];
+struct ReleaseTicket { void operator()(MgsTicket* t) const { mgs_ledger_release(t); } };
+using Ticket = std::unique_ptr<MgsTicket, ReleaseTicket>;
+
+void sync_device(void* ctx) {
+  MaybeReleaseGil nogil;
+  c10::hip::HIPGuard g(*static_cast<int*>(ctx));
+  (void)hipDeviceSynchronize();
 }
 
-// non-blocking read of a forward's status words (manigaussian_amd/_state.py Pending.poll)
-int poll(PendingRec& p) {
-  if (p.rc != MGS_PENDING || p.recovered) return p.rc;
-  const volatile uint64_t* w = p.slot;
-  if (w[0] == ~0ull && w[1] == ~0ull) return p.rc;
-  int32_t nr = -1, ch = -1, ref = -1;
-  const int rc = mgs_forward_result(&p.a, p.slot, &nr, &ch, &ref);
-  if (nr >= 0) p.num_rendered = nr;
-  if (ch >= 0) p.chunks_used = ch;
-  if (ref >= 0) p.ref_rendered = ref;
-  if (rc != MGS_PENDING) p.rc = rc;
-  return rc;
-}
-
-// Fold a finished forward into the marks (mu held); returns an error message if the call must raise ("" otherwise) and
-// appends warnings to `warnings` (issued by the caller outside the lock).
-std::string account(DeviceState& st, PendingRec& p, int rc, std::vector<std::string>* warnings) {
-  if (rc == MGS_OK) { st.learn(p.key, p.num_rendered, p.chunks_used, false); return ""; }
-  if (rc == MGS_NEED_CAPACITY || rc == MGS_RETRY_TABLE_INIT) {
-    std::string msg;
-    if (rc == MGS_NEED_CAPACITY) {
-      const int cap = p.a.binning_capacity;
-      const bool over_inst = p.num_rendered > cap && cap > 0;
-      st.learn(p.key, p.num_rendered, -1, !over_inst);
-      std::string what = over_inst ? std::to_string(p.num_rendered) + " (Gaussian, tile) instances > capacity " + std::to_string(cap)
-                                   : "chunk pool of " + std::to_string(p.a.chunk_pool) + " records";
-      msg = std::string(kOutgrew) + " (" + what + "): the images of THAT call were incomplete.  The marks are raised";
-    } else {  // nothing to learn: the scene did not grow, a workgroup of the preprocess launch was held back
-      msg = std::string(kHandshake) + ": the images of THAT call were incomplete";
-    }
-    const int policy = cfg().policy.load();
-    if (p.recovered || (policy == POLICY_REPAIR && p.recoverable && !p.backward_enqueued)) {
-      warnings->push_back(msg + "; the call's backward re-renders on the blocking path before it runs, but a loss computed "
-                                "from those images was computed from incomplete images." +
-                          (rc == MGS_NEED_CAPACITY ? "  For scenes that grow abruptly use manigaussian_amd.set_forward_mode('safe') "
-                                                     "(the default) or a larger set_headroom()."
-                                                   : "  manigaussian_amd.set_options(table_init=1) removes the hand-shake."));
-      return "";
-    }
-    if (p.recoverable && !p.backward_enqueued) {  // overflow policy "raise"
-      p.recovered = true;                         // its backward, if it still comes, raises too
-      return msg + "; the step is lost (overflow policy 'raise'): re-run it" +
-             (rc == MGS_NEED_CAPACITY ? ", or use manigaussian_amd.set_forward_mode('safe') (the default) for scenes that grow abruptly."
-                                      : ".");
-    }
-    return msg + " and its gradients were computed on the incomplete state; re-run the step" +
-           (rc == MGS_NEED_CAPACITY ? ", or use manigaussian_amd.set_forward_mode('safe') (the default) for scenes that grow abruptly."
-                                    : " (manigaussian_amd.set_options(table_init=1) removes the hand-shake).");
-  }
-  return std::string("rasterizer forward failed: ") + mgs_last_error() + " (code " + std::to_string(rc) + ")";
-}
-
-// Read every report that has arrived (wait: all of them, synchronising with the device once if one is outstanding).
-// Three steps, so that the device's mutex is NEVER held across the GIL's release / re-acquisition -- the lock order is GIL ->
-// mutex everywhere (a second Python thread on the same device blocks on the mutex while it holds the GIL): poll under the lock;
-// synchronise outside it; account under the lock again.  `deferred`: append the warnings there instead of issuing them (callers
-// that hold a lock of their own -- a node's -- issue them after dropping it: warn_runtime takes the GIL).
-void drain(DeviceState& st, bool wait, std::vector<std::string>* deferred = nullptr) {
-  std::string failed;
-  std::vector<std::string> warnings;
-  // reports that were outstanding when the device was synchronised.  Shared pointers, not addresses: another thread's drain may
-  // account and free a record in the meantime, and a forward enqueued AFTER the synchronisation may be allocated at that very
-  // address -- it would pass for "must have reported" (found by the two-thread stress test)
-  std::vector<std::shared_ptr<PendingRec>> must_finish;
-  bool need_sync = false;
-  {
-    std::lock_guard<std::mutex> lk(st.mu);
-    if (st.pending.empty()) return;
-    const size_t n = st.pending.size();
-    size_t kept = 0;
-    for (size_t i = 0; i < n; i++) {
-      const std::shared_ptr<PendingRec>& p = st.pending[i];
-      if (poll(*p) != MGS_PENDING) continue;
-      if (wait || (n - i - 1) + kept >= (size_t)NSLOTS / 2) { need_sync = true; must_finish.push_back(p); }
-      else kept++;
-    }
-  }
-  if (need_sync) {  // everything enqueued so far has run after this: a report of must_finish that is still missing never comes
-    MaybeReleaseGil nogil;
-    c10::hip::HIPGuard g(st.index);
-    (void)hipDeviceSynchronize();
-  }
-  {
-    std::lock_guard<std::mutex> lk(st.mu);
-    std::deque<std::shared_ptr<PendingRec>> keep;
-    for (std::shared_ptr<PendingRec>& p : st.pending) {
-      const int rc = poll(*p);
-      if (rc == MGS_PENDING) {
-        if (std::find(must_finish.begin(), must_finish.end(), p) != must_finish.end()) {
-          if (failed.empty()) failed = "a rasterizer forward finished without reporting its instance count";
-        } else {
-          keep.push_back(p);  // (enqueued by another thread in the meantime, or not yet due)
-        }
-        continue;
-      }
-      std::string f = account(st, *p, rc, &warnings);
-      if (failed.empty()) failed = f;
-    }
-    st.pending.swap(keep);
-  }
+// Read every report of the device that has arrived (wait: all of them): the ledger learns, this binding says what it hands back.
+// `deferred`: append the warnings there instead of issuing them (callers that hold a lock of their own -- a node's -- issue them
+// after dropping it: warn_runtime takes the GIL).
+void drain(int dev, bool wait, std::vector<std::string>* deferred = nullptr) {
+  MgsLedgerOut out;
+  if (mgs_ledger_drain(dev, wait, &sync_device, &dev, &out) != MGS_OK) fail(mgs_last_error());
+  if (!out.error && !out.n_warnings) return;
+  const std::string failed = out.error ? out.error : "";  // (copies: the texts live until this thread's next ledger call)
+  const std::vector<std::string> warnings(out.warnings, out.warnings + out.n_warnings);
   if (deferred) deferred->insert(deferred->end(), warnings.begin(), warnings.end());
   else for (const std::string& w : warnings) warn_runtime(w);
   if (!failed.empty()) fail(failed);
@@ -336,7 +179,8 @@ const char* kBackwardTwice =
 // 104-164), called by the engine without entering Python -------------------------------------------------------------------
 struct MgsRasterizeBackward : public Node {
   MgsRasterArgs a;                       // the forward's arguments, reused as they were
-  std::shared_ptr<PendingRec> pending;   // its outstanding device report (nullptr: settled in the forward)
+  Ticket pending;                        // its outstanding device report in the ledger (nullptr: settled in the forward)
+  MgsMarkKey key{};                      // the marks key of its shape
   std::vector<SavedVariable> saved;      // the reference's saved inputs: colors, feature, means3D, scales, rotations, cov3D, sh
   at::Tensor opacities, bg, viewmatrix, projmatrix, campos;  // kept alive (the argument struct holds their addresses)
   at::Tensor radii, ws, binning2, grad_buffer;
@@ -361,14 +205,14 @@ struct MgsRasterizeBackward : public Node {
   }
   variable_list apply(variable_list&& grads) override;
   variable_list apply_locked(variable_list&& grads, std::vector<std::string>* warnings);
-  void settle(DeviceState& st, hipStream_t stream, std::vector<std::string>* warnings);
-  void recover(DeviceState& st, hipStream_t stream, bool handshake_only);
+  void settle(hipStream_t stream, std::vector<std::string>* warnings);
+  void recover(hipStream_t stream, bool handshake_only, int32_t binned);
 };
 
 // The asynchronous forward of this backward outgrew its workspace and the report is in: bin and render it AGAIN with room
 // (capacity from the count the device reported, worst-case chunk pool: cannot overflow) into the same output tensors, so that the
 // backward runs on a complete state (manigaussian_amd/_C.py recover_forward).
-void MgsRasterizeBackward::recover(DeviceState& st, hipStream_t stream, bool handshake_only) {
+void MgsRasterizeBackward::recover(hipStream_t stream, bool handshake_only, int32_t binned) {
   if (handshake_only) {
     // the scene did not outgrow anything: a workgroup of the preprocess launch gave up waiting for workgroup 0's zeroed tables.
     // Same workspace, tables zeroed by a launch of their own this time (no workgroup waits for another).
@@ -377,7 +221,7 @@ void MgsRasterizeBackward::recover(DeviceState& st, hipStream_t stream, bool han
   } else {
     const MgsPlanShape shape = plan_shape(P, M, include_feature ? F : 0, W, H);
     int64_t cap = 0, pool = 0;
-    check_rc(mgs_plan_capacity(&shape, MGS_SIZE_COUNT, std::max<int64_t>(pending->num_rendered, 0), 0, 1.0, 1.0, &cap, &pool),
+    check_rc(mgs_plan_capacity(&shape, MGS_SIZE_COUNT, std::max<int64_t>(binned, 0), 0, 1.0, 1.0, &cap, &pool),
              "mgs_plan_capacity");
     const size_t nbytes = mgs_plan_binning_bytes(&shape, cap, 0, 0);
     if (!nbytes) fail(mgs_last_error());
@@ -392,10 +236,7 @@ void MgsRasterizeBackward::recover(DeviceState& st, hipStream_t stream, bool han
   a.bwd_accum_bytes = 0;
   uint64_t* slot;
   uint32_t tag;
-  {
-    std::lock_guard<std::mutex> lk(st.mu);
-    slot = st.take_slot(&tag);
-  }
+  check_rc(mgs_ledger_take_slot(device_index, &slot, &tag), "status slot");
   a.status_tag = tag;
   int32_t nr = 0;
   const auto f32 = radii.options().dtype(at::kFloat);
@@ -411,44 +252,32 @@ void MgsRasterizeBackward::recover(DeviceState& st, hipStream_t stream, bool han
                                    include_feature ? of.data_ptr<float>() : nullptr, &nr, slot, stream),
              "rasterizer forward (re-run after a workspace overflow)");
   }
-  auto np = std::make_shared<PendingRec>();
-  np->a = a; np->slot = slot; np->key = pending->key;
-  {
-    std::lock_guard<std::mutex> lk(st.mu);
-    pending->recovered = true;
-    st.pending.push_back(np);
-  }
-  pending = np;
+  Ticket rerun(mgs_ledger_add(device_index, &a, 0, slot, &key, 0));  // (the marks learn the binned count from its report)
+  if (!rerun) fail(mgs_last_error());
+  mgs_ledger_superseded(pending.get());
+  pending = std::move(rerun);
   num_rendered = nr;
   counters().recovered++;
 }
 
 // Backward entry: what is known about this backward's forward?  (manigaussian_amd/_C.py _settle)
-void MgsRasterizeBackward::settle(DeviceState& st, hipStream_t stream, std::vector<std::string>* warnings) {
+void MgsRasterizeBackward::settle(hipStream_t stream, std::vector<std::string>* warnings) {
   if (!pending) return;
-  int rc;
-  {
-    std::lock_guard<std::mutex> lk(st.mu);
-    rc = poll(*pending);
-  }
+  MgsReport report;
+  const int rc = mgs_ledger_poll(pending.get(), &report);
   if (rc == MGS_NEED_CAPACITY || rc == MGS_RETRY_TABLE_INIT) {
-    if (cfg().policy.load() == POLICY_RAISE) {
-      drain(st, false, warnings);  // folds the report into the marks and raises ... unless an earlier drain already did
-      fail(rc == MGS_NEED_CAPACITY
-               ? "the asynchronous rasterizer forward of this backward outgrew its workspace (the scene grew past the head-room over "
-                 "earlier calls of its shape): its images are incomplete and the step is lost; the next call of the shape gets a "
-                 "larger workspace (overflow policy 'raise')"
-               : std::string(kHandshake) + ": its images are incomplete and the step is lost (overflow policy 'raise')");
+    MgsLedgerConfig config;
+    mgs_ledger_get_config(&config);
+    if (config.overflow_policy == MGS_OVERFLOW_RAISE) {
+      drain(device_index, false, warnings);  // folds the report into the marks and raises ... unless an earlier drain already did
+      fail(mgs_ledger_lost_step_message(rc));
     }
-    drain(st, false, warnings);  // learn + warn (this pending is recoverable and its backward has not been enqueued: no raise)
-    recover(st, stream, rc == MGS_RETRY_TABLE_INIT);
+    drain(device_index, false, warnings);  // learn + warn (this ticket is recoverable and its backward has not been enqueued: no raise)
+    recover(stream, rc == MGS_RETRY_TABLE_INIT, report.num_rendered);
     return;
   }
-  if (rc != MGS_OK && rc != MGS_PENDING) drain(st, false, warnings);
-  if (rc == MGS_PENDING) {
-    std::lock_guard<std::mutex> lk(st.mu);
-    pending->backward_enqueued = true;  // too late to repair: if this forward overflowed, the next drain raises
-  }
+  if (rc != MGS_OK && rc != MGS_PENDING) drain(device_index, false, warnings);
+  if (rc == MGS_PENDING) mgs_ledger_backward_enqueued(pending.get());  // too late to repair: if this forward overflowed, the next drain raises
 }
 
 // The node's mutex is never held while a warning is issued (warn_runtime takes the GIL; a Python thread that holds the GIL may
@@ -487,9 +316,8 @@ variable_list MgsRasterizeBackward::apply_locked(variable_list&& grads, std::vec
     if (!g_feat.is_contiguous()) g_feat = g_feat.contiguous();
   }
   hipStream_t stream = c10::hip::getCurrentHIPStream(device_index).stream();
-  DeviceState& st = state(device_index);
   clk.lap(SB_UNPACK);
-  settle(st, stream, warnings);
+  settle(stream, warnings);
   clk.lap(SB_SETTLE);
   const MgsPlanShape shape = plan_shape(P, M, include_feature ? F : 0, W, H);
   MgsGradientPlan L;
@@ -544,9 +372,11 @@ py::object rasterize(const at::Tensor& means3D, const at::Tensor& means2D, const
                      int64_t degree, bool prefiltered, bool debug, bool include_feature) {
   SegClock clk;
   Config& C = cfg();
-  const int mode = C.mode.load();
+  MgsLedgerConfig ledger;
+  mgs_ledger_get_config(&ledger);
+  const int mode = ledger.mode;
   auto decline = [&]() { counters().declined++; return py::none(); };
-  if (!C.enabled.load() || debug || prefiltered || mode == MODE_BLOCKING) return decline();
+  if (!C.enabled.load() || debug || prefiltered || mode == MGS_MODE_BLOCKING) return decline();
   if (!means3D.defined() || !means3D.is_cuda() || means3D.dim() != 2 || means3D.size(1) != 3) return decline();  // (Python raises)
   const int64_t P = means3D.size(0);
   if (P == 0 || H <= 0 || W <= 0) return decline();
@@ -570,24 +400,17 @@ py::object rasterize(const at::Tensor& means3D, const at::Tensor& means2D, const
   hipStream_t stream = c10::hip::getCurrentHIPStream(di).stream();
   if (is_capturing(stream)) return decline();
   DeviceState& st = state(di);
+  ensure_ring(di);  // (the device's one ring of status slots: this binding's pinned block, or the ctypes shim's)
   clk.lap(SG_STREAM);
-  // reports of forwards the Python shim enqueued; and, once per device, the shim's own state (its pinned status ring cannot
-  // be allocated later, inside a HIP-graph capture -- which is the shim's job)
-  if (g_py_drain && ((di < MAX_DEVICES && g_py_pending[di].load() > 0) || !st.python_side_built)) {
-    (*g_py_drain)(di);
-    st.python_side_built = true;
-  }
-  drain(st, false);  // reports of earlier forwards that have arrived: learn their counts, raise if one overflowed
+  drain(di, false);  // reports of earlier forwards (either binding's) that have arrived: learn their counts, raise if one overflowed
   clk.lap(SG_DRAIN);
 
   MgsOptions opt;
-  double head_inst;
-  int64_t safe_bytes;
   {
     std::lock_guard<std::mutex> lk(C.mu);
-    opt = C.opt; head_inst = C.head_inst; safe_bytes = C.safe_bytes;
+    opt = C.opt;
   }
-  (void)head_inst;
+  int64_t safe_bytes = ledger.safe_bytes;
   if (safe_bytes < 0) {  // the default budget: 1/32 of this device's memory, at least 1 GB
     if (st.auto_safe_bytes == 0) {
       size_t total = 0;
@@ -596,7 +419,8 @@ py::object rasterize(const at::Tensor& means3D, const at::Tensor& means2D, const
     }
     safe_bytes = st.auto_safe_bytes;
   }
-  const Key key{0, (int32_t)P, (int32_t)W, (int32_t)H, (int32_t)F, opt.tight_bins};
+  // (V = 0: a single view; the ctypes shim's batches have keys of their own)
+  const MgsMarkKey key{0, 0, (int32_t)P, (int32_t)W, (int32_t)H, (int32_t)F, opt.tight_bins};
   // the arena's sizes, and the worst case: every Gaussian in every tile, every chunk of every block visited
   const MgsPlanShape shape = plan_shape(P, M, F, W, H);
   struct ArenaMemo { MgsPlanShape shape; int64_t budget; int rc; MgsArenaPlan plan; };  // the library's answer for the last shape
@@ -619,33 +443,30 @@ py::object rasterize(const at::Tensor& means3D, const at::Tensor& means2D, const
   at::Tensor ws;
   std::shared_ptr<Lease> lease;
   size_t bb = 0;
-  bool worst = mode != MODE_ASYNC && plan.worst_fits;
+  bool worst = mode != MGS_MODE_ASYNC && plan.worst_fits;
   if (worst) {
     bb = plan.worst_bytes;
-    if (st.held_bytes.load() + (int64_t)bb > safe_bytes) {
+    if (!mgs_ledger_hold(di, (int64_t)bb, safe_bytes)) {
       worst = false;
     } else {
+      lease = std::make_shared<Lease>(di, (int64_t)bb);  // (the node's if a backward follows; else it ends with this call)
       try {
         ws = at::empty({(int64_t)(gb + ib + bb)}, u8);
-        if (want_grad) lease = std::make_shared<Lease>(&st, (int64_t)bb);  // (without a backward the workspace dies with this call)
       } catch (const c10::OutOfMemoryError&) {
         worst = false;
         ws = at::Tensor();
+        lease.reset();
       }
     }
     if (!worst) counters().budget_fallbacks++;
   }
   int64_t cap = 0, pool = 0, mark_R = 0;
   bool have_guess = worst;
-  {
-    std::lock_guard<std::mutex> lk(st.mu);
-    if (worst) { cap = plan.worst_capacity; pool = plan.worst_pool; }
-    else have_guess = st.guess(key, shape, &cap, &pool);
-    auto it = st.marks.find(key);
-    if (it != st.marks.end()) mark_R = it->second.R;
-  }
-  const bool lazy = have_guess && (mode == MODE_ASYNC || (mode == MODE_SAFE && worst));
-  if (mode == MODE_ASYNC && !lazy) return decline();  // first calls of a shape in async mode: the Python path learns the marks
+  if (worst) { cap = plan.worst_capacity; pool = plan.worst_pool; }
+  else have_guess = mgs_marks_guess(di, &key, &cap, &pool) == 1;
+  (void)mgs_marks_get(di, &key, &mark_R, nullptr);
+  const bool lazy = have_guess && (mode == MGS_MODE_ASYNC || (mode == MGS_MODE_SAFE && worst));
+  if (mode == MGS_MODE_ASYNC && !lazy) return decline();  // first calls of a shape in async mode: the Python path learns the marks
   // wait for the preprocess: capacity from the mark (0: none yet), worst-case pool for that capacity (cannot overflow)
   if (!lazy) check_rc(mgs_plan_capacity(&shape, MGS_SIZE_COUNT, mark_R ? mark_R : -1, 0, 1.0, 1.0, &cap, &pool), "mgs_plan_capacity");
 
@@ -697,10 +518,7 @@ py::object rasterize(const at::Tensor& means3D, const at::Tensor& means2D, const
   }
   uint64_t* slot;
   uint32_t tag;
-  {
-    std::lock_guard<std::mutex> lk(st.mu);
-    slot = st.take_slot(&tag);
-  }
+  check_rc(mgs_ledger_take_slot(di, &slot, &tag), "status slot");
   a.status_tag = tag;
   int32_t nr = 0;
   int rc;
@@ -713,7 +531,7 @@ py::object rasterize(const at::Tensor& means3D, const at::Tensor& means2D, const
     rc = mgs_rasterize_forward(&a, radii.data_ptr<int32_t>(), out_color.data_ptr<float>(), feat_ptr, &nr, slot, stream);
     counters().waited++;
   }
-  std::shared_ptr<PendingRec> pending;
+  Ticket pending;
   at::Tensor binning2;
   if (rc == MGS_NEED_CAPACITY) {  // (waiting path) first call of the shape, or the scene grew: bin + render again with room
     const int64_t binned = (int64_t)(uint32_t)(*(volatile uint64_t*)slot);
@@ -725,23 +543,20 @@ py::object rasterize(const at::Tensor& means3D, const at::Tensor& means2D, const
     a.binning = binning2.data_ptr(); a.binning_bytes = nb; a.binning_capacity = (int32_t)cap2; a.chunk_pool = 0;
     check_rc(mgs_rasterize_forward_render(&a, nr, radii.data_ptr<int32_t>(), out_color.data_ptr<float>(), feat_ptr, stream),
              "rasterize_gaussians");
-    std::lock_guard<std::mutex> lk(st.mu);
-    st.learn(key, binned, -1, false);
+    (void)mgs_marks_learn(di, &key, binned, -1, 0);
     counters().retried++;
   } else {
     check_rc(rc, "rasterize_gaussians");
-    pending = std::make_shared<PendingRec>();
-    pending->a = a; pending->slot = slot; pending->key = key;
-    pending->recoverable = want_grad;
-    std::lock_guard<std::mutex> lk(st.mu);
-    st.pending.push_back(pending);
+    // a forward that a backward will follow can be repaired there if it overflowed (recover)
+    pending.reset(mgs_ledger_add(di, &a, 0, slot, &key, want_grad ? MGS_TICKET_RECOVERABLE : 0));
+    if (!pending) fail(mgs_last_error());
   }
   counters().forwards++;
   clk.lap(SG_LIBRARY);
   if (want_grad) {
     std::shared_ptr<MgsRasterizeBackward> node(new MgsRasterizeBackward(), torch::autograd::deleteNode);
     node->set_next_edges(torch::autograd::collect_next_edges(means3D, means2D, sh, colors, feat, opacities, scales, rotations, cov3D));
-    node->a = a; node->pending = pending; node->device_index = di;
+    node->a = a; node->pending = std::move(pending); node->key = key; node->device_index = di;
     node->num_rendered = lazy ? -1 : nr;
     node->P = P; node->M = M; node->F = F; node->H = H; node->W = W; node->include_feature = include_feature;
     node->saved.reserve(7);
@@ -760,57 +575,7 @@ py::object rasterize(const at::Tensor& means3D, const at::Tensor& means2D, const
   return ret;
 }
 
-// ---- configuration and the marks, driven by manigaussian_amd/_state.py and _lib.py ----------------------------------------
-Key key_of(const py::tuple& t) {
-  if (t.size() == 5) return Key{0, t[0].cast<int>(), t[1].cast<int>(), t[2].cast<int>(), t[3].cast<int>(), t[4].cast<int>()};
-  if (t.size() == 7) return Key{t[1].cast<int>(), t[2].cast<int>(), t[3].cast<int>(), t[4].cast<int>(), t[5].cast<int>(), t[6].cast<int>()};
-  if (t.size() == 8 && t[0].cast<std::string>() == "sets")
-    return Key{t[2].cast<int>(), t[3].cast<int>(), t[4].cast<int>(), t[5].cast<int>(), t[6].cast<int>(), t[7].cast<int>(),
-               t[1].cast<int>()};
-  throw py::key_error("a marks key is (P, W, H, F, tight_bins), ('views', V, P, W, H, F, tight_bins) or "
-                      "('sets', S, V, P, W, H, F, tight_bins)");
-}
-py::tuple tuple_of(const Key& k) {
-  if (k.V == 0) return py::make_tuple(k.P, k.W, k.H, k.F, k.tight);
-  if (k.S > 0) return py::make_tuple("sets", k.S, k.V, k.P, k.W, k.H, k.F, k.tight);
-  return py::make_tuple("views", k.V, k.P, k.W, k.H, k.F, k.tight);
-}
-
-py::object marks_get(int dev, const py::tuple& key) {
-  DeviceState& st = state(dev);
-  std::lock_guard<std::mutex> lk(st.mu);
-  auto it = st.marks.find(key_of(key));
-  if (it == st.marks.end()) return py::none();
-  py::list l;
-  l.append(it->second.R);
-  l.append(it->second.chunks < 0 ? py::object(py::none()) : py::object(py::int_(it->second.chunks)));
-  return std::move(l);
-}
-void marks_set(int dev, const py::tuple& key, int64_t R, py::object chunks) {
-  DeviceState& st = state(dev);
-  std::lock_guard<std::mutex> lk(st.mu);
-  Mark& m = st.marks[key_of(key)];
-  m.R = R;
-  m.chunks = chunks.is_none() ? -1 : chunks.cast<int64_t>();
-}
-bool marks_del(int dev, const py::tuple& key) {
-  DeviceState& st = state(dev);
-  std::lock_guard<std::mutex> lk(st.mu);
-  return st.marks.erase(key_of(key)) != 0;
-}
-py::list marks_keys(int dev) {
-  DeviceState& st = state(dev);
-  std::lock_guard<std::mutex> lk(st.mu);
-  py::list l;
-  for (auto& kv : st.marks) l.append(tuple_of(kv.first));
-  return l;
-}
-
-void configure(int mode, int policy, double head_inst, double head_chunks, int64_t safe_bytes) {
-  Config& C = cfg();
-  std::lock_guard<std::mutex> lk(C.mu);
-  C.mode = mode; C.policy = policy; C.head_inst = head_inst; C.head_chunks = head_chunks; C.safe_bytes = safe_bytes;
-}
+// ---- this binding's own switches, driven by manigaussian_amd/_lib.py and _C.py ---------------------------------------------
 void set_options(int tight_bins, int fast_exp, int exact_cull, int bin_mode, int seg, int gm_waves, int dbg, int table_init) {
   Config& C = cfg();
   std::lock_guard<std::mutex> lk(C.mu);
@@ -819,30 +584,12 @@ void set_options(int tight_bins, int fast_exp, int exact_cull, int bin_mode, int
 }
 bool set_enabled(bool on) { return cfg().enabled.exchange(on); }
 
-void check_status(int dev, bool wait) {  // dev < 0: every device used so far
-  std::vector<DeviceState*> all;
-  {
-    std::lock_guard<std::mutex> lk(g_states_mu);
-    for (auto& s : g_states)
-      if (s && (dev < 0 || s->index == dev)) all.push_back(s.get());
-  }
-  for (DeviceState* s : all) drain(*s, wait);
+void check_status(int dev, bool wait) {  // dev < 0: every device that has a ring
+  for (int d = 0; d < MGS_LEDGER_MAX_DEVICES; d++)
+    if ((dev < 0 || d == dev) && mgs_ledger_ring(d, nullptr, 0)) drain(d, wait);
 }
-int pending_count(int dev) {
-  DeviceState& st = state(dev);
-  std::lock_guard<std::mutex> lk(st.mu);
-  return (int)st.pending.size();
-}
-void set_python_drain(py::object fn) {
-  delete g_py_drain;
-  g_py_drain = fn.is_none() ? nullptr : new py::object(std::move(fn));
-}
-void set_python_pending(int dev, int n) {
-  if (dev >= 0 && dev < MAX_DEVICES) g_py_pending[dev] = n;
-}
-// the ctypes shim's worst-case workspaces are charged against the same per-device sum (manigaussian_amd/_state.py hold())
-int64_t hold_add(int dev, int64_t delta) { return state(dev).held_bytes += delta; }
-int64_t held_bytes(int dev) { return state(dev).held_bytes.load(); }
+int pending_count(int dev) { return mgs_ledger_outstanding(dev); }
+int64_t held_bytes(int dev) { return mgs_ledger_held(dev); }
 
 py::dict profile_read(bool reset) {
   py::dict d;
@@ -874,19 +621,11 @@ PYBIND11_MODULE(_mgs_torch, m) {
   m.attr("ABI_VERSION") = MGS_ABI_VERSION;
   m.def("build_id", []() { return std::string(mgs_build_id()); });
   m.def("rasterize", &rasterize);
-  m.def("configure", &configure);
   m.def("set_options", &set_options);
   m.def("set_enabled", &set_enabled);
   m.def("enabled", []() { return cfg().enabled.load(); });
   m.def("check_status", &check_status, py::arg("device") = -1, py::arg("wait") = true);
   m.def("pending_count", &pending_count);
-  m.def("marks_get", &marks_get);
-  m.def("marks_set", &marks_set);
-  m.def("marks_del", &marks_del);
-  m.def("marks_keys", &marks_keys);
-  m.def("set_python_drain", &set_python_drain);
-  m.def("set_python_pending", &set_python_pending);
-  m.def("hold_add", &hold_add);
   m.def("held_bytes", &held_bytes);
   m.def("counters", &counters_dict, py::arg("reset") = false);
   m.def("set_profile", [](bool on) { return g_profile.exchange(on); });

@@ -134,7 +134,8 @@ def test_async_workspace_guess_follows_the_marks_and_the_headroom():
     from manigaussian_amd import _state
     import manigaussian_amd as mg
     st = _state.DeviceState.__new__(_state.DeviceState)  # no pinned memory needed for the marks
-    st.marks = {}
+    st.marks = _state._Marks(9)  # (the ledger's marks of a device index nothing else uses)
+    st.marks.clear()
     key = (1000, 64, 64, 3, 1)
     assert st.guess(key) is None
     st.learn(key, R=10000, chunks=None, pool_unknown=True)

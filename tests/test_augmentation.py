@@ -67,7 +67,7 @@ def test_workspace_bytes():
     assert L.mgs_se3_workspace_bytes(1) >= 64 and L.mgs_se3_workspace_bytes(_lib.SE3_MAX_BATCH) >= 64 * _lib.SE3_MAX_BATCH
     assert L.mgs_se3_workspace_bytes(8) % 256 == 0
     assert augmentation.workspace_bytes(8) == L.mgs_se3_workspace_bytes(8)
-    assert L.mgs_abi_version() == 16  # additive exports
+    assert L.mgs_abi_version() == 17  # additive exports
 
 
 def test_the_library_refuses_bad_arguments_before_any_launch():

@@ -31,7 +31,7 @@ def test_compiled_binding_loads_declines_cpu_calls_and_shares_the_marks():
     before = e.counters()["declined"]
     assert e.rasterize(t, t, t, t, t, t, t, t, t, t, t, t, t, 8, 8, 1.0, 1.0, 1.0, 1, False, False, True) is None
     assert e.counters()["declined"] == before + 1
-    m = _state._Marks(e, 7)  # (device index 7: nothing else uses it)
+    m = _state._Marks(7)  # (device index 7: nothing else uses it; the one store of the library's ledger)
     key, vkey = (1000, 64, 64, 3, 1), ("views", 4, 1000, 64, 64, 3, 1)
     assert key not in m and m.get(key) is None
     m[key] = [10000, None]
@@ -426,6 +426,49 @@ def test_safe_budget_is_charged_against_the_workspaces_live_forwards_hold(compil
         gc.collect()
         torch.cuda.synchronize()
         assert _state.held_bytes(dev.index) == 0
+
+
+@pytest.mark.gpu
+def test_both_bindings_ask_one_ledger():
+    """The marks and the outstanding reports are the library's (csrc/mgs_ledger.hip), not a binding's: a shape the ctypes shim
+    warmed up is known to the compiled binding -- its FIRST forward of the shape is lazy --, and an overflow behind the compiled
+    path is reported by the shim's check_status()."""
+    e = _ext()
+    dev, d, rast, dC, dF = _setup(2000, 3, W=64)
+    key = (2000, 64, 64, 3, 1)
+    old_mode, old_budget = mg.set_forward_mode("async"), _state._SAFE_BYTES
+    mg.set_safe_workspace(0)
+    try:
+        mg.check_status(dev)
+        st = _state.device_state(dev)
+        st.marks.pop(key, None)  # (whoever warms the shape below is the shim)
+        with _C.use_compiled(False):
+            for _ in range(3):
+                ref = _step(d, rast, dC, dF)
+                mg.check_status(dev)
+        good = list(st.marks[key])
+        assert good[0] > 0 and good[1] is not None
+        e.counters(True)
+        got = _step(d, rast, dC, dF)
+        n = e.counters()
+        assert n["forwards"] == 1 and n["backwards"] == 1 and n["declined"] == 0 and n["waited"] == 0, n
+        mg.check_status(dev)
+        _same(ref, got)
+        # too few chunk records (the shape bins fewer instances than the 4096 every guess adds: an instance mark cannot be too low)
+        st.marks[key] = [good[0], 1]
+        assert st.guess(key)[1] < good[1]
+        with torch.no_grad():          # (no backward will follow: nobody can repair it)
+            rast(d["means3D"], torch.zeros_like(d["means3D"]), d["opacities"], shs=d["shs"],
+                 language_feature_precomp=d["language_feature"], scales=d["scales"], rotations=d["rotations"])
+        assert e.counters()["forwards"] == 2 and e.counters()["declined"] == 0
+        with pytest.raises(RuntimeError, match="outgrew the workspace"):
+            _state.check_status(dev)
+        assert st.marks[key][0] >= good[0]
+        _same(ref, _step(d, rast, dC, dF))
+        mg.check_status(dev)
+    finally:
+        mg.set_forward_mode(old_mode)
+        _state.set_safe_bytes(old_budget)
 
 
 @pytest.mark.gpu

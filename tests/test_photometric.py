@@ -284,11 +284,11 @@ def test_cpu_tensors_and_bad_arguments_are_refused_with_a_message():
 
 
 def test_library_refuses_bad_shapes_with_a_message_and_sizes_its_workspace():
-    """The C ABI's own argument checks (no device needed: they come before any launch), the workspace query, ABI 16."""
+    """The C ABI's own argument checks (no device needed: they come before any launch), the workspace query, the ABI version."""
     L = _lib.lib()
-    assert _lib.ABI_VERSION == 16 and L.mgs_abi_version() == 16
+    assert _lib.ABI_VERSION == 17 and L.mgs_abi_version() == 17
     with open(os.path.join(ROOT, "include", "mgsplat.h")) as f:
-        assert re.search(r"#define MGS_ABI_VERSION 16\b", f.read())
+        assert re.search(r"#define MGS_ABI_VERSION 17\b", f.read())
     fwd = lambda V, C, W, H, *p: L.mgs_photometric_forward(V, C, W, H, *(p or [None] * 9), 0, None)  # noqa: E731
     assert fwd(2, 65, 8, 8) == _lib.MGS_ERR_INVALID_ARG and "C = 65" in _lib.last_error()
     assert fwd(17, 3, 8, 8) == _lib.MGS_ERR_INVALID_ARG and "V = 17" in _lib.last_error()

@@ -846,6 +846,41 @@ int mgs_bias_geglu_backward(int64_t rows, int64_t M, const float* h, int64_t h_s
                             int64_t g_stride, float* dh, float* dbias, void* workspace, size_t workspace_bytes, int row_split,
                             mgs_stream_t stream);
 
+/* ---- the voxel encoder stem's normalisation sites, fused, fp32 (MG/helpers/network_utils.py:219-231, class InPlaceABN:
+ * nn.BatchNorm3d then an in-place nn.LeakyReLU; :297-303, the skip adds behind three of them) -- additive exports, ABI v17 ----
+ * x, residual (or NULL), y, g_y, dx: [B, C, N] contiguous, 16-byte aligned, N = D H W; a row is one (batch, channel).
+ *   z = (x - mean_c) invstd_c weight_c + bias_c;   y = residual + (z > 0 ? z : negative_slope z)      (negative_slope 0: ReLU)
+ * training != 0: mean_c and the BIASED variance var_c over the channel's B N values, invstd_c = 1 / sqrt(var_c + eps);
+ *   running_mean_c = (1 - momentum) running_mean_c + momentum mean_c, running_var_c likewise with the UNBIASED variance
+ *   var_c B N / (B N - 1), both in place (both NULL: not tracked); *num_batches_tracked (int64, or NULL) += 1 by the same launch;
+ *   stats [C, 2] = (mean_c, invstd_c): all the backward keeps beside x.  Two launches.  A row is cut into nsub sub-slices of whole
+ *   16-byte vectors, nsub a function of N alone (1..64); the first launch reduces every sub-slice to a (count, mean, M2) record in
+ *   the workspace (Chan's merge from register tiles up; never sum x^2 - (sum x)^2), the second merges a channel's B nsub records in a
+ *   fixed order, in double, and writes y.  slices (0: chosen from B C and N; 1..64: forced, a test aid; never more than nsub) is
+ *   the number of workgroups that share a row's sub-slices: no result depends on it, bit for bit.
+ * training == 0: mean_c = running_mean_c, var_c = running_var_c; one launch, nothing is updated; stats and workspace are unused.
+ * backward (of a training forward): dz = g_y (z > 0 ? 1 : negative_slope), z recomputed from x and stats by the forward's own
+ *   expression (z == 0 takes the slope, as torch does);  xhat = (x - mean_c) invstd_c;
+ *   dbias_c = sum dz;  dweight_c = sum dz xhat;  dx = weight_c invstd_c (dz - dbias_c / (B N) - xhat dweight_c / (B N)).
+ *   Two launches: per sub-slice records of the two sums, then dx (and dweight, dbias: either may be NULL) from their merge, in the
+ *   same fixed order.  The gradient towards residual is g_y itself.
+ * workspace: 16-byte aligned, at least mgs_abn_workspace_bytes(B, C, N) bytes (64 records per row: independent of N and of the
+ * split; 0 for sizes outside the limits).
+ * MGS_ERR_INVALID_ARG before any launch: C outside 1..65536; B or N < 1; N > 2^31 - 1; B C > (2^31 - 1) / 64; negative_slope, eps or
+ * momentum not finite, eps < 0; slices outside [0, 64]; B N < 2 in training mode ("Expected more than 1 value per channel when
+ * training"); a NULL pointer other than the optional ones (running buffers must be both or neither, and are needed in eval mode); a
+ * volume or the workspace not 16-byte aligned.  MGS_ERR_WORKSPACE: fewer bytes than the query's.  Element offsets are 64-bit.
+ * No atomics, no workgroup waits for another, nothing to zero: bit-identical from run to run.  No host read, no allocation, no
+ * state: capturable into a HIP graph (every replay updates the running buffers and the counter once). */
+size_t mgs_abn_workspace_bytes(int64_t B, int C, int64_t N);
+int mgs_abn_forward(int64_t B, int C, int64_t N, const float* x, const float* residual, const float* weight, const float* bias,
+                    float* running_mean, float* running_var, int64_t* num_batches_tracked, int training, float momentum, float eps,
+                    float negative_slope, float* y, float* stats, void* workspace, size_t workspace_bytes, int slices,
+                    mgs_stream_t stream);
+int mgs_abn_backward(int64_t B, int C, int64_t N, const float* x, const float* g_y, const float* weight, const float* bias,
+                     const float* stats, float negative_slope, float* dx, float* dweight, float* dbias, void* workspace,
+                     size_t workspace_bytes, int slices, mgs_stream_t stream);
+
 /* Per-stage device timing (hipEvents on the caller's stream), enabled with
  * mgs_set_option("profile", 1) (render backward only) or 2 (every stage).  mgs_profile_read waits for the
  * recorded events, writes the summed milliseconds and launch counts per stage ([mgs_profile_num_stages()]),

@@ -254,6 +254,11 @@ _EXPORTS = {
     "mgs_bias_geglu_forward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, c_fp, ctypes.c_int64, c_fp, c_fp, c_fp]),
     "mgs_bias_geglu_backward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, c_fp, ctypes.c_int64, c_fp, c_fp, ctypes.c_int64,
                                                c_fp, c_fp, c_fp, c_sz, ctypes.c_int, c_fp]),
+    "mgs_abn_workspace_bytes": (c_sz, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64]),
+    "mgs_abn_forward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64] + [c_fp] * 7 + [ctypes.c_int] +
+                        [ctypes.c_float] * 3 + [c_fp, c_fp, c_fp, c_sz, ctypes.c_int, c_fp]),
+    "mgs_abn_backward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64] + [c_fp] * 5 + [ctypes.c_float] +
+                         [c_fp] * 4 + [c_sz, ctypes.c_int, c_fp]),
     "mgs_forward_stats": (ctypes.c_int, [ctypes.POINTER(MgsRasterArgs), c_i32, ctypes.POINTER(ctypes.c_int64),
                                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), c_fp]),
     "mgs_debug_geom_layout": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(c_sz)] * 4),

@@ -182,6 +182,82 @@ __device__ __forceinline__ float half_last(float v, int lane) {
   return (lane & 32) ? b : a;
 }
 
+// Exclusive SUFFIX sum over the lanes of each 32-lane half, plus a per-lane addend: lane i gets y + v[i+1] + ... + v[31 of its
+// half] (the last lane: y; the whole sum is the first lane's result plus its input).  Summed from the back ON PURPOSE: the render
+// backward needs "what lies behind me", and forming it as (total - inclusive prefix) cancels where the front of the list
+// outweighs its back -- behind a Gaussian whose alpha saturates at 0.99 the transmittance drops a hundredfold, the difference
+// keeps the rounding error of the front's large terms, and the division by 1 - alpha = 0.01 multiplies it by another hundred
+// (measured on the saturated-alpha scenes of tests/edge_scenes.py: 1e-4 per Gaussian against a float32 yardstick of 2e-6).
+// row_shl steps inside the rows of 16 (the mirror image of the prefix scans above); the exclusive form is the last step, which
+// adds the left neighbour's sum (zero fill past the row's end) to the addend.  Nothing broadcasts a row's FIRST lane to the row
+// before it, so the sum of a half's second row (its lane 16 / 48 after the row scans) crosses by v_readlane and is added to the
+// half's first row alone under a narrowed EXEC (put back before the block ends): two adds instead of a select, an add and a
+// select.  One asm block, like the scans above.
+__device__ __forceinline__ float half_excl_suffix_add(float v, float y) {
+  float r = v, e;
+  uint32_t s16, s48;
+  unsigned long long sv;
+  asm volatile(
+      "s_nop 1\n\t"
+      "v_add_f32_dpp %0, %5, %0 row_shl:1 row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %0, %5, %0 row_shl:2 row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %0, %5, %0 row_shl:3 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\t"
+      "v_add_f32_dpp %0, %0, %0 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\t"
+      "v_add_f32_dpp %0, %0, %0 row_shl:8 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\t"
+      "v_add_f32_dpp %1, %0, %6 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_readlane_b32 %2, %0, 16\n\t"
+      "v_readlane_b32 %3, %0, 48\n\t"
+      "s_mov_b64 %4, exec\n\t"
+      "s_mov_b64 exec, 0xffff\n\t"
+      "v_add_f32 %1, %2, %1\n\t"
+      "s_lshl_b64 exec, exec, 32\n\t"
+      "v_add_f32 %1, %3, %1\n\t"
+      "s_mov_b64 exec, %4"
+      : "+&v"(r), "=&v"(e), "=&s"(s16), "=&s"(s48), "=&s"(sv) : "v"(v), "v"(y) : "scc");
+  return e;
+}
+// two at a time, the chains interleaved like half_incl_scan_add2: a <- ya + what lies behind a's lane, b likewise
+__device__ __forceinline__ void half_excl_suffix_add2(float& a, float& b, float ya, float yb) {
+  float ra = a, rb = b, ea, eb;
+  uint32_t a16, a48, b16, b48;
+  unsigned long long sv;
+  asm volatile(
+      "s_nop 1\n\t"
+      "v_add_f32_dpp %0, %9, %0 row_shl:1 row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %1, %10, %1 row_shl:1 row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %0, %9, %0 row_shl:2 row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %1, %10, %1 row_shl:2 row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %0, %9, %0 row_shl:3 row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %1, %10, %1 row_shl:3 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 0\n\t"
+      "v_add_f32_dpp %0, %0, %0 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %1, %1, %1 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 0\n\t"
+      "v_add_f32_dpp %0, %0, %0 row_shl:8 row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %1, %1, %1 row_shl:8 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 0\n\t"
+      "v_add_f32_dpp %2, %0, %11 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_add_f32_dpp %3, %1, %12 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_readlane_b32 %4, %0, 16\n\t"
+      "v_readlane_b32 %6, %1, 16\n\t"
+      "v_readlane_b32 %5, %0, 48\n\t"
+      "v_readlane_b32 %7, %1, 48\n\t"
+      "s_mov_b64 %8, exec\n\t"
+      "s_mov_b64 exec, 0xffff\n\t"
+      "v_add_f32 %2, %4, %2\n\t"
+      "v_add_f32 %3, %6, %3\n\t"
+      "s_lshl_b64 exec, exec, 32\n\t"
+      "v_add_f32 %2, %5, %2\n\t"
+      "v_add_f32 %3, %7, %3\n\t"
+      "s_mov_b64 exec, %8"
+      : "+&v"(ra), "+&v"(rb), "=&v"(ea), "=&v"(eb), "=&s"(a16), "=&s"(a48), "=&s"(b16), "=&s"(b48), "=&s"(sv)
+      : "v"(a), "v"(b), "v"(ya), "v"(yb) : "scc");
+  a = ea; b = eb;
+}
+
 constexpr int ilog2(int n) { return n <= 1 ? 0 : 1 + ilog2(n / 2); }
 constexpr int next_pow2(int n) { int p = 1; while (p < n) p *= 2; return p; }
 

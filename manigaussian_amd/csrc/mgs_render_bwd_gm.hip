@@ -11,8 +11,8 @@
 //   the lane walks its 32 pixels p(u, r, h) = 32u + (r&3) + 8(r>>2) + 4h serially, so every per-Gaussian sum
 //   (mean2D, conic, opacity, colour) is a private register accumulation -- no cross-lane reduction at all;
 //   per pixel, transmittance is an exclusive prefix PRODUCT of (1-alpha) over the group's lanes and the
-//   "colour behind" term an exclusive suffix SUM of D*alpha*T  (DPP row_shr / row_bcast15 scans over each
-//   32-lane half):  accum_rec.dL = S/T_after  =>  dL/dalpha = D*T - (S + T_final*bg.dL)/(1-alpha);
+//   "colour behind" term an exclusive suffix SUM of D*alpha*T, summed from the back  (DPP row_shr / row_bcast15 and
+//   row_shl scans over each 32-lane half):  accum_rec.dL = S/T_after  =>  dL/dalpha = D*T - (S + T_final*bg.dL)/(1-alpha);
 //   the two dense contractions over channels run on the matrix cores in exact fp32 (v_mfma_f32_32x32x2_f32,
 //   bit-for-bit an fmaf chain): D[pixel][Gaussian] = dL[pixel][ch] . row[Gaussian][ch]  (K = channels), and
 //   dL_dfeature[ch][Gaussian] += dL[pixel][ch] * (alpha*T)[pixel][Gaussian]  (K = pixels).  The pixel order
@@ -423,11 +423,9 @@ __global__ void __launch_bounds__(NW * 64, TWO ? 4 : 1) gm_bwd_kernel(RenderArgs
             const f32x2 D = {Dt[rr], Dt[rr + 1]};
             const f32x2 Dw = D * wa;
             float q0 = Dw.x, q1 = Dw.y;
-            half_incl_scan_add2(q0, q1);
-            const f32x2 tot = {half_last(q0, lane), half_last(q1, lane)};
-            const f32x2 sy = {s0.y, s1.y};
-            const f32x2 S = (tot - f32x2{q0, q1}) + sy;
-            if (g > 0 && n == 0) { pd[w][pp].y = sy.x + tot.x; pd[w][pp + 1].y = sy.y + tot.y; }
+            half_excl_suffix_add2(q0, q1, s0.y, s1.y);  // summed from the back: no (total - prefix) cancellation
+            const f32x2 S = {q0, q1};                   // D*alpha*T of everything behind me (+ bg term)
+            if (g > 0 && n == 0) { pd[w][pp].y = S.x + Dw.x; pd[w][pp + 1].y = S.y + Dw.y; }  // (the first lane: everything)
             const f32x2 rom = {__builtin_amdgcn_rcpf(om.x), __builtin_amdgcn_rcpf(om.y)};
             const f32x2 dLa_ = D * T - S * rom;
             const f32x2 dLa = {act0 ? dLa_.x : 0.f, act1 ? dLa_.y : 0.f};
@@ -475,10 +473,8 @@ __global__ void __launch_bounds__(NW * 64, TWO ? 4 : 1) gm_bwd_kernel(RenderArgs
           const float wa = act ? alpha * T : 0.f;
           const float D = Dt[rr];
           const float Dw = D * wa;
-          const float P = half_incl_scan_add(Dw);
-          const float tot = half_last(P, lane);
-          const float S = (tot - P) + st.y;                          // D*alpha*T of everything behind me (+ bg term)
-          if (g > 0 && n == 0) pd[w][pp].y = st.y + tot;             // group g-1 sees this group behind it
+          const float S = half_excl_suffix_add(Dw, st.y);            // D*alpha*T of everything behind me (+ bg term)
+          if (g > 0 && n == 0) pd[w][pp].y = S + Dw;                 // group g-1 sees this group behind it (the first lane: all)
           const float dL_dalpha = act ? D * T - S * __builtin_amdgcn_rcpf(om) : 0.f;
           const float dL_dG = op * dL_dalpha;
           const float gdx = G * dx, gdy = G * dy;

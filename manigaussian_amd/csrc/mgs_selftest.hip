@@ -58,6 +58,17 @@ __global__ void selftest_kernel(int* result) {
     float pa = m, pb = m2;
     half_excl_scan_mul2(pa, pb, lane);
     if (pa != em || pb != em2) bad |= 1 << 27;
+    // exclusive suffix sums (the render backward's "what lies behind me"), one and two at a time
+    float xa = 0.f, xa2 = 0.f;
+    for (int i = n + 1; i < 32; i++) {
+      xa += (float)((((lane & 32) + i) * 5) % 7 + 1);
+      xa2 += (float)((((lane & 32) + i) * 3) % 5 + 1);
+    }
+    const float y1 = (float)(100 + lane), y2 = (float)(300 - lane);  // the per-lane addends
+    if (half_excl_suffix_add(a, y1) != xa + y1) bad |= (int)0x80000000u;
+    float ua = a, ub = a2;
+    half_excl_suffix_add2(ua, ub, y1, y2);
+    if (ua != xa + y1 || ub != xa2 + y2) bad |= (int)0x80000000u;
   }
   {  // the fp32 MFMA the render kernels use is exact fp32: C = A (32x2) * B (2x32) with small integers
     using f32x16 = __attribute__((ext_vector_type(16))) float;

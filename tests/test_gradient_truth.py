@@ -150,16 +150,15 @@ def _need_gpu():
     return _lib
 
 
-def _hip_case(tag, name):
-    """CASES[name] through util.run_hip under the options in force, gated against the shared truth."""
-    case = gt.CASES[name]
-    (sc, cam, kw, dC, dF), T = gt.case_truth(name)
-    inc = case.get("include_feature", True)
-    ch, fh, rh, gh = util.run_hip(sc, cam, dC, dF, case.get("sh_degree", 1), inc, case.get("bg", gt.BG),
-                                  scale_modifier=case.get("scale_modifier", 1.0))
+def _hip_scene(tag, s, T, few=None):
+    """A scene tuple (sc, cam, kw, dC, dF) through util.run_hip under the options in force, gated against its truth T (few:
+    the cap on the NUMBER of fragile pixels where a share of the image says nothing).  Returns what run_hip returned."""
+    sc, cam, kw, dC, dF = s
+    inc = bool(kw["include_feature"])
+    ch, fh, rh, gh = util.run_hip(sc, cam, dC, dF, kw["sh_degree"], inc, tuple(kw["bg"].tolist()),
+                                  scale_modifier=kw["scale_modifier"])
     assert torch.equal(rh, T.radii), "radii differ"
     T = gt.follow(T, ch, fh if inc else None)
-    few = 2 if name.startswith("one_block") else None  # the 8x8 image marks 2 of its 64 pixels: at most 2 pixels
     gt.gate_image(tag, "color", ch, T.images["color"], T.fragile_px, T.image_yard["color"], max_fragile_pixels=few)
     if inc:
         assert fh.shape == T.images["feature"].shape
@@ -169,6 +168,16 @@ def _hip_case(tag, name):
     got = {util.GRAD_KEYS[k]: v for k, v in gh.items() if util.GRAD_KEYS[k] in T.grads}
     assert set(got) == set(T.grads), (sorted(got), sorted(T.grads))
     gt.gate_gradients(tag, T, got)
+    return ch, fh, rh, gh
+
+
+def _hip_case(tag, name):
+    """CASES[name] through the HIP path, gated against the shared truth."""
+    s, T = gt.case_truth(name)
+    kw, case = s[2], gt.CASES[name]
+    assert (kw["sh_degree"], bool(kw["include_feature"]), kw["scale_modifier"]) == (
+        case.get("sh_degree", 1), case.get("include_feature", True), case.get("scale_modifier", 1.0))
+    _hip_scene(tag, s, T, few=2 if name.startswith("one_block") else None)  # the 8x8 image marks 2 of its 64 pixels
 
 
 @gpu

@@ -150,7 +150,10 @@ def test_early_termination_excludes_the_terminating_gaussian():
 
 def test_finite_differences_float64():
     """Oracle A's autograd (float64) against central differences, the independent gradient pin
-    (SURVEY.md 8c v).  Q1/Q2 quirk regions (saturated alpha, clamped frustum) are avoided by the scene."""
+    (SURVEY.md 8c v).  Q1/Q2 quirk regions (saturated alpha, clamped frustum) are avoided by THIS scene: there the reference's
+    backward is not the derivative of its forward, and differences would not agree.  They are covered by
+    tests/test_edge_scenes.py (saturated_alpha_*, near_plane_*: Oracle A's modelling of both quirks against Oracle B and a
+    float64 truth, and the HIP path against all three)."""
     torch.manual_seed(0)
     sc, cam, kw, dC, dF = util.scene_case(P=40, F=3, W=32, H=32, neg=False)
     sc["opacities"] = sc["opacities"].clamp(0.05, 0.6)

@@ -881,6 +881,40 @@ int mgs_abn_backward(int64_t B, int C, int64_t N, const float* x, const float* g
                      const float* stats, float negative_slope, float* dx, float* dweight, float* dbias, void* workspace,
                      size_t workspace_bytes, int slices, mgs_stream_t stream);
 
+/* ---- the voxel encoder stem's 3x3x3 convolutions, direct, fp32 (MG/helpers/network_utils.py:234-306: the bias-free nn.Conv3d of
+ * ConvBnReLU3D and the nn.ConvTranspose3d(stride 2) of the three up sites) -- additive exports, ABI v17 ----
+ * Kernel 3x3x3, padding 1, dilation 1, groups 1, no bias; the three spatial strides are equal, stride = 1 or 2; Cin, Cout = 1..64.
+ * x [B, Cin, D, H, W], y and g_y [B, Cout, OD, OH, OW] with O = (I - 1) / stride + 1 per dimension (integer division), dx like x,
+ * w and dw [Cout, Cin, 3, 3, 3] (nn.Conv3d's layout): all contiguous and 16-byte aligned.  D, H, W are ALWAYS the extents of the
+ * convolution's input side (x, dx); the output side's are derived from them, so the two cannot disagree.
+ *   forward:          y[b,co,o]     = sum_ci sum_tap w[co,ci,tap] x[b,ci,o stride + tap - 1]      (taps outside the volume read 0)
+ *   backward_data:    dx[b,ci,i]    = sum_co sum_{(o,tap): o stride + tap - 1 = i} w[co,ci,tap] g_y[b,co,o]
+ *   backward_weight:  dw[co,ci,tap] = sum_b sum_o g_y[b,co,o] x[b,ci,o stride + tap - 1]
+ * All three gather: every output element is written once, by one thread; backward_data at stride 2 works per 2x2x2 block of dx (1, 2,
+ * 4 or 8 taps per voxel by parity class), not as a scatter.  backward_weight is two launches: the forward's output tiles, in their
+ * linear order, are cut into at most 64 runs whose number and length depend on the shape alone; every run is summed to one RECORD
+ * [Cout, Cin, 27] in the workspace, and the second launch adds the records in ascending order, in double.  split (0: chosen from the
+ * shape; 1..64: forced, a test aid; never more than the number of runs) is the number of workgroups that share the runs of one
+ * (4 output channels, input channel) pair: it says which workgroup computes a record, never what the record is -- dw is the same
+ * bits for every split.
+ * nn.ConvTranspose3d(Cin_T, Cout_T, 3, stride 2, padding 1, output_padding 0 or 1) needs no entry point of its own: its weight
+ * [Cin_T, Cout_T, 27] IS a convolution weight [Cout, Cin, 27] with Cout = Cin_T, Cin = Cout_T; its forward is backward_data with D H W
+ * = its output extents 2 I_T - 1 + output_padding, its input gradient is forward, its weight gradient is backward_weight with x = the
+ * gradient of its output and g_y = its input.
+ * workspace: 16-byte aligned, at least as many bytes as the size query returns for the same shape (0 for sizes outside the limits).
+ * MGS_ERR_INVALID_ARG before any launch: Cin or Cout outside 1..64; stride other than 1 or 2; B or an extent below 1; D H W >= 2^31
+ * (elements per (batch, channel) row), or B times the number of tiles above 2^31 - 1; a NULL pointer; a pointer not 16-byte aligned;
+ * split outside [0, 64].  MGS_ERR_WORKSPACE: fewer bytes than the query's.  Element offsets are 64-bit.
+ * No atomics, no workgroup waits for another, nothing to zero: bit-identical from run to run.  No host read, no allocation, no
+ * state: capturable into a HIP graph. */
+size_t mgs_conv3d_workspace_bytes(int64_t B, int Cin, int Cout, int64_t D, int64_t H, int64_t W, int stride);
+int mgs_conv3d_forward(int64_t B, int Cin, int Cout, int64_t D, int64_t H, int64_t W, int stride, const float* x, const float* w,
+                       float* y, mgs_stream_t stream);
+int mgs_conv3d_backward_data(int64_t B, int Cin, int Cout, int64_t D, int64_t H, int64_t W, int stride, const float* g_y,
+                             const float* w, float* dx, mgs_stream_t stream);
+int mgs_conv3d_backward_weight(int64_t B, int Cin, int Cout, int64_t D, int64_t H, int64_t W, int stride, const float* x,
+                               const float* g_y, float* dw, void* workspace, size_t workspace_bytes, int split, mgs_stream_t stream);
+
 /* Per-stage device timing (hipEvents on the caller's stream), enabled with
  * mgs_set_option("profile", 1) (render backward only) or 2 (every stage).  mgs_profile_read waits for the
  * recorded events, writes the summed milliseconds and launch counts per stage ([mgs_profile_num_stages()]),

@@ -17,6 +17,7 @@ from .spatial_softmax import SpatialSoftmax3D, spatial_softmax3d  # noqa: F401
 from .volume import Conv3DBlock, Conv3DUpsampleBlock, resample_pad  # noqa: F401
 from .feedforward import GEGLU, FeedForward, PreNorm, bias_geglu, layer_norm  # noqa: F401
 from .encoder import ConvBnReLU3D, InPlaceABN, MultiLayer3DEncoderShallow, batch_norm_act  # noqa: F401
+from .conv3d import conv3d, conv_transpose3d  # noqa: F401
 from .augmentation import (Se3Augmentation, apply_se3_augmentation,  # noqa: F401
                            apply_se3_augmentation_with_camera_pose)
 from . import camera  # noqa: F401

@@ -259,6 +259,13 @@ _EXPORTS = {
                         [ctypes.c_float] * 3 + [c_fp, c_fp, c_fp, c_sz, ctypes.c_int, c_fp]),
     "mgs_abn_backward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64] + [c_fp] * 5 + [ctypes.c_float] +
                          [c_fp] * 4 + [c_sz, ctypes.c_int, c_fp]),
+    "mgs_conv3d_workspace_bytes": (c_sz, [ctypes.c_int64, ctypes.c_int, ctypes.c_int] + [ctypes.c_int64] * 3 + [ctypes.c_int]),
+    "mgs_conv3d_forward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int] + [ctypes.c_int64] * 3 + [ctypes.c_int] +
+                           [c_fp] * 4),
+    "mgs_conv3d_backward_data": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int] + [ctypes.c_int64] * 3 +
+                                 [ctypes.c_int] + [c_fp] * 4),
+    "mgs_conv3d_backward_weight": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int] + [ctypes.c_int64] * 3 +
+                                   [ctypes.c_int] + [c_fp] * 4 + [c_sz, ctypes.c_int, c_fp]),
     "mgs_forward_stats": (ctypes.c_int, [ctypes.POINTER(MgsRasterArgs), c_i32, ctypes.POINTER(ctypes.c_int64),
                                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), c_fp]),
     "mgs_debug_geom_layout": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(c_sz)] * 4),

@@ -11,7 +11,9 @@ MultiLayer3DEncoderShallow) with its ten normalisation sites fused (csrc/mgs_abn
 
 `InPlaceABN`, `ConvBnReLU3D` and `MultiLayer3DEncoderShallow` have the reference's constructors, attribute and parameter names and
 initialisation (InPlaceABN keeps a real nn.BatchNorm3d as `bn`): the stem's 62 state_dict entries load with strict=True and the other
-way round.  The convolutions stay torch's.  The stem hands conv4 / conv2 / conv0 to its three transposed-convolution sites as the
+way round.  The 3x3x3 convolutions are nn.Conv3d / nn.ConvTranspose3d modules whose weights go through conv3d / conv_transpose3d
+(conv3d.py, csrc/mgs_conv3d.hip) where conv_site() says so (CONV overrides it; a CPU tensor, another dtype, a bias or any other
+kernel size, padding, dilation or groups stays torch's, and so does the 1x1x1 conv_out).  The stem hands conv4 / conv2 / conv0 to its three transposed-convolution sites as the
 skip tensor.  A site runs the reference's torch composition on a CPU tensor, for a dtype other than float32, for momentum=None, in
 eval mode with gradients enabled -- and wherever fused_site() says the fused op was not measured faster (FORCE overrides it).
 """
@@ -19,8 +21,10 @@ import torch
 from torch import nn
 
 from . import _lib, _ops
+from .conv3d import _readable, conv3d, conv_transpose3d
 
 MAX_C = 65536
+MAX_CONV_C = 64
 
 # Which sites the drop-in modules send through batch_norm_act (the function itself always takes the kernels).  FORCE: None = follow
 # fused_site(); True / False = every eligible site fused / none (tests, scripts/bench_encoder.py).
@@ -43,11 +47,54 @@ def fused_site(values_per_channel, channels):
     return values_per_channel * channels >= FUSED_MIN_ELEMENTS
 
 
-def _readable(t):
-    """The tensor itself when the kernels can read it in place (contiguous, 16-byte aligned), else one contiguous copy."""
-    if t.is_contiguous() and t.data_ptr() % 16 == 0:
-        return t
-    return t.contiguous() if not t.is_contiguous() else t.clone()
+# Which of the stem's 3x3x3 convolutions the drop-in modules send through conv3d / conv_transpose3d (csrc/mgs_conv3d.hip).  CONV: None =
+# follow conv_site(); True / False = every eligible site / none (tests, scripts/bench_conv3d.py).  FORCE = False keeps them on torch too.
+CONV = None
+CONV_MIN_VOXELS = 50 ** 3          # the smallest measured winner's input volume (conv2: [16, 50^3] -> [16, 50^3], stride 1)
+CONV_MIN_VOXELS_STRIDED = 100 ** 3   # ... and the smallest with stride 2, transposed or not (conv1, conv11: a 100^3 input side)
+
+
+def conv_site(cin, cout, voxels, stride, transposed):
+    """The routing rule of the convolutions (voxels = D H W of the convolution's input; for a transposed site, of its OUTPUT, the
+    input side of the convolution it transposes), from the measurement (scripts/bench_conv3d.py -> profiles/conv3d_bench.json,
+    DESIGN.md 7m), by fused_site()'s criterion: a site is routed only where the op's third quartile lay below torch's first quartile
+    for forward AND forward + backward, eager AND graph-replayed, torch taken at the faster of cudnn.benchmark off and on.  On an
+    MI355X at B = 1 that holds for conv0, conv1, conv2 and conv11 (forward 1.3 to 5.1 x, forward + backward 58 to 262 x: torch's
+    weight gradient alone takes 18 to 147 ms there).  At a 50^3 input side with stride 2 (conv3) and at 25^3 (conv4) the op wins
+    forward + backward 6.9 / 6.6 x but loses the forward alone (133 against 45 us, 116 against 75 us); conv9 (transposed, 50^3
+    output) won its forward by 5 % in the committed run and lost it by 1 % in the run before: inside the spread between runs; at
+    25^3 with stride 2 and at 13^3 (conv5, conv6, conv7) the op loses every pair: a few dozen workgroups on 256 CUs.  Those six
+    stay torch's.  Nothing was measured between the sizes or at other channel counts: the thresholds are the winners' own volumes."""
+    if stride == 1 and not transposed:
+        return voxels >= CONV_MIN_VOXELS
+    return voxels >= CONV_MIN_VOXELS_STRIDED
+
+
+def _conv_routed(conv, x, transposed):
+    """Whether `conv` (a bias-free 3x3x3 nn.Conv3d / stride-2 nn.ConvTranspose3d of the stem's kind) on x goes through the kernels."""
+    if CONV is False or FORCE is False or not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
+        return False
+    w = conv.weight
+    if x.dim() != 5 or x.numel() == 0 or conv.bias is not None or w.dtype != torch.float32 or w.device != x.device:
+        return False
+    if conv.kernel_size != (3, 3, 3) or conv.padding != (1, 1, 1) or conv.dilation != (1, 1, 1) or conv.groups != 1:
+        return False
+    if conv.padding_mode != "zeros" or max(w.shape[:2]) > MAX_CONV_C or x.size(1) != conv.in_channels:
+        return False
+    if transposed:
+        op = conv.output_padding
+        if conv.stride != (2, 2, 2) or op not in ((0, 0, 0), (1, 1, 1)):
+            return False
+        voxels = (2 * x.size(2) - 1 + op[0]) * (2 * x.size(3) - 1 + op[0]) * (2 * x.size(4) - 1 + op[0])
+        cin, cout = conv.out_channels, conv.in_channels   # of the convolution it transposes
+    else:
+        if conv.stride not in ((1, 1, 1), (2, 2, 2)):
+            return False
+        voxels = x[0, 0].numel()
+        cin, cout = conv.in_channels, conv.out_channels
+    if voxels >= 2 ** 31:
+        return False
+    return True if CONV else conv_site(cin, cout, voxels, conv.stride[0], transposed)
 
 
 class _BatchNormAct(torch.autograd.Function):
@@ -186,6 +233,8 @@ class ConvBnReLU3D(nn.Module):
         self.bn = norm_act(out_channels)
 
     def forward(self, x):
+        if _conv_routed(self.conv, x, False):
+            return self.bn(conv3d(x, self.conv.weight, self.conv.stride[0]))
         return self.bn(self.conv(x))
 
 
@@ -197,9 +246,14 @@ def _up_site(cin, cout, output_padding, norm_act):
 
 def _up(site, x, skip):
     """skip + site(x): the add goes into the norm_act when it is ours."""
+    conv = site[0]
+    if isinstance(conv, nn.ConvTranspose3d) and _conv_routed(conv, x, True):
+        y = conv_transpose3d(x, conv.weight, conv.output_padding[0])
+    else:
+        y = conv(x)
     if len(site) == 2 and isinstance(site[1], InPlaceABN):
-        return site[1](site[0](x), residual=skip)
-    return skip + site(x)
+        return site[1](y, residual=skip)
+    return skip + site[1:](y)
 
 
 class MultiLayer3DEncoderShallow(nn.Module):

@@ -915,6 +915,34 @@ int mgs_conv3d_backward_data(int64_t B, int Cin, int Cout, int64_t D, int64_t H,
 int mgs_conv3d_backward_weight(int64_t B, int Cin, int Cout, int64_t D, int64_t H, int64_t W, int stride, const float* x,
                                const float* g_y, float* dw, void* workspace, size_t workspace_bytes, int split, mgs_stream_t stream);
 
+/* ---- the voxel encoder stem's pointwise (1x1x1) convolution with bias (helpers/network_utils.py:248-306, conv_out =
+ * nn.Conv3d(8, 64, 1, bias=True)) -- additive exports, ABI v17 ----
+ * Kernel 1x1x1, stride 1, no padding, groups 1; Cin, Cout = 1..64; n = D H W, the voxels of a (batch, channel) row.
+ * x and dx [B, Cin, n], y and g_y [B, Cout, n], w and dw [Cout, Cin] (nn.Conv3d's [Cout, Cin, 1, 1, 1]), bias and db [Cout]: all
+ * contiguous and 16-byte aligned.
+ *   forward:   y[b,co,v]  = bias[co] + sum_ci w[co,ci] x[b,ci,v]                      (bias may be NULL: no bias)
+ *   backward:  dx[b,ci,v] = sum_co w[co,ci] g_y[b,co,v];  dw[co,ci] = sum_{b,v} g_y[b,co,v] x[b,ci,v];  db[co] = sum_{b,v} g_y[b,co,v]
+ * Every output element is written once, by one thread; every sum's order depends on the shape alone.  The forward is one launch;
+ * where n is a multiple of 4 its accesses are 16 bytes wide.  dx, dw and db may each be NULL and only what is asked for is computed:
+ * dx alone is one launch without a workspace (x may then be NULL); with dw or db the voxel tiles, in their linear order over (batch,
+ * voxel), are cut into at most 64 runs whose number and length depend on the shape alone, every run is summed to one RECORD
+ * [Cout, Cin + 1] in the workspace by a launch that reads g_y once for dx, dw and db together when Cin <= 16 (once per 16 input channels
+ * above), and a second launch adds the records in ascending order, in double.  split (0: chosen from the shape; 1..64: forced, a test
+ * aid; never more than the number of runs) is the number of workgroups that share the runs: it says which workgroup computes a
+ * record, never what the record is -- dw and db are the same bits for every split.
+ * workspace: 16-byte aligned, at least as many bytes as the size query returns for the same shape (0 for sizes outside the limits,
+ * else a multiple of 256).
+ * MGS_ERR_INVALID_ARG before any launch: Cin or Cout outside 1..64; B or n below 1; n >= 2^31, or B times the number of tiles above
+ * 2^31 - 1; a NULL pointer where one is required (dx, dw and db all NULL included); a pointer not 16-byte aligned; split outside
+ * [0, 64].  MGS_ERR_WORKSPACE: fewer bytes than the query's.  Element offsets are 64-bit.
+ * No atomics, no workgroup waits for another, nothing to zero: bit-identical from run to run.  No host read, no allocation, no
+ * state: capturable into a HIP graph. */
+size_t mgs_pointwise_workspace_bytes(int64_t B, int Cin, int Cout, int64_t n);
+int mgs_pointwise_forward(int64_t B, int Cin, int Cout, int64_t n, const float* x, const float* w, const float* bias, float* y,
+                          mgs_stream_t stream);
+int mgs_pointwise_backward(int64_t B, int Cin, int Cout, int64_t n, const float* x, const float* g_y, const float* w, float* dx,
+                           float* dw, float* db, void* workspace, size_t workspace_bytes, int split, mgs_stream_t stream);
+
 /* Per-stage device timing (hipEvents on the caller's stream), enabled with
  * mgs_set_option("profile", 1) (render backward only) or 2 (every stage).  mgs_profile_read waits for the
  * recorded events, writes the summed milliseconds and launch counts per stage ([mgs_profile_num_stages()]),

@@ -13,8 +13,9 @@ MultiLayer3DEncoderShallow) with its ten normalisation sites fused (csrc/mgs_abn
 initialisation (InPlaceABN keeps a real nn.BatchNorm3d as `bn`): the stem's 62 state_dict entries load with strict=True and the other
 way round.  The 3x3x3 convolutions are nn.Conv3d / nn.ConvTranspose3d modules whose weights go through conv3d / conv_transpose3d
 (conv3d.py, csrc/mgs_conv3d.hip) where conv_site() says so (CONV overrides it; a CPU tensor, another dtype, a bias or any other
-kernel size, padding, dilation or groups stays torch's, and so does the 1x1x1 conv_out).  The stem hands conv4 / conv2 / conv0 to its three transposed-convolution sites as the
-skip tensor.  A site runs the reference's torch composition on a CPU tensor, for a dtype other than float32, for momentum=None, in
+kernel size, padding, dilation or groups stays torch's).  The 1x1x1 conv_out with bias goes through pointwise_conv3d (pointwise.py,
+csrc/mgs_pointwise.hip) where pointwise_site() says so (POINTWISE overrides it).  The stem hands conv4 / conv2 / conv0 to its three
+transposed-convolution sites as the skip tensor.  A site runs the reference's torch composition on a CPU tensor, for a dtype other than float32, for momentum=None, in
 eval mode with gradients enabled -- and wherever fused_site() says the fused op was not measured faster (FORCE overrides it).
 """
 import torch
@@ -22,6 +23,7 @@ from torch import nn
 
 from . import _lib, _ops
 from .conv3d import _readable, conv3d, conv_transpose3d
+from .pointwise import pointwise_conv3d
 
 MAX_C = 65536
 MAX_CONV_C = 64
@@ -95,6 +97,46 @@ def _conv_routed(conv, x, transposed):
     if voxels >= 2 ** 31:
         return False
     return True if CONV else conv_site(cin, cout, voxels, conv.stride[0], transposed)
+
+
+# Whether the stem's 1x1x1 conv_out goes through pointwise_conv3d (csrc/mgs_pointwise.hip).  POINTWISE: None = follow pointwise_site();
+# True / False = every eligible site / none (tests, scripts/bench_pointwise.py).  FORCE = False keeps it on torch too; FORCE = True
+# and CONV = True do not switch it on.
+POINTWISE = None
+POINTWISE_CHANNELS = (8, 64)  # the channel counts that were measured (conv_out's)
+POINTWISE_MIN_VALUES = 50 ** 3  # B D H W of the smallest measured winner, [1, 8 -> 64, 50^3] (None: no measured shape won all four pairs)
+
+
+def pointwise_site(cin, cout, values_per_channel):
+    """The routing rule of the 1x1x1 convolution (values_per_channel = B D H W), from the measurement (scripts/bench_pointwise.py ->
+    profiles/pointwise_bench.json), by fused_site()'s criterion: a shape is routed only where the op's third quartile
+    lay below torch's first quartile for forward AND forward + backward, eager AND graph-replayed, torch taken at the faster of
+    cudnn.benchmark off and on.  Measured on an MI355X at 8 -> 64 channels, B = 1: at 100^3 (conv_out) the op wins the forward 5.7 x
+    and forward + backward 400 x (0.33 against 132 ms: torch's weight and bias gradient alone takes 126 ms), at 50^3 2.3 x and 86 x;
+    at 25^3 it wins forward + backward 16 x but loses the forward alone (31 against 22 us eager, 34 against 16 us graph-replayed), so
+    25^3 is not routed.  Nothing else was measured, so nothing else is routed: the threshold is the smallest winner's own size, at
+    its own channel counts."""
+    if POINTWISE_MIN_VALUES is None:
+        return False
+    return (cin, cout) == POINTWISE_CHANNELS and values_per_channel >= POINTWISE_MIN_VALUES
+
+
+def _pointwise_routed(conv, x):
+    """Whether `conv` (a 1x1x1 nn.Conv3d of conv_out's kind, with or without a bias) on x goes through the kernels."""
+    if POINTWISE is False or FORCE is False or not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
+        return False
+    w, b = conv.weight, conv.bias
+    if x.dim() != 5 or x.numel() == 0 or w.dtype != torch.float32 or w.device != x.device:
+        return False
+    if b is not None and (b.dtype != torch.float32 or b.device != x.device):
+        return False
+    if conv.kernel_size != (1, 1, 1) or conv.stride != (1, 1, 1) or conv.padding != (0, 0, 0) or conv.dilation != (1, 1, 1):
+        return False
+    if conv.groups != 1 or conv.padding_mode != "zeros" or max(w.shape[:2]) > MAX_CONV_C or x.size(1) != conv.in_channels:
+        return False
+    if x[0, 0].numel() >= 2 ** 31:
+        return False
+    return True if POINTWISE else pointwise_site(conv.in_channels, conv.out_channels, x.numel() // x.size(1))
 
 
 class _BatchNormAct(torch.autograd.Function):
@@ -293,4 +335,6 @@ class MultiLayer3DEncoderShallow(nn.Module):
         voxel_list.append(x)
         x = _up(self.conv11, x, conv0)
         del conv0
+        if _pointwise_routed(self.conv_out, x):
+            return pointwise_conv3d(x, self.conv_out.weight, self.conv_out.bias), voxel_list
         return self.conv_out(x), voxel_list

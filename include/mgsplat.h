@@ -943,6 +943,40 @@ int mgs_pointwise_forward(int64_t B, int Cin, int Cout, int64_t n, const float* 
 int mgs_pointwise_backward(int64_t B, int Cin, int Cout, int64_t n, const float* x, const float* g_y, const float* w, float* dx,
                            float* dw, float* db, void* workspace, size_t workspace_bytes, int split, mgs_stream_t stream);
 
+/* ---- the Perceiver decoder's narrow-output 3x3x3 convolution with its pad folded into the addressing (SURVEY.md 2:
+ * agents/manigaussian_bc/perceiver_lang_io.py:322, trans_decoder = nn.Conv3d(128, 1, 3, padding=1, padding_mode='replicate') with
+ * bias) -- additive exports, ABI v17 ----
+ * Kernel 3x3x3, stride 1, padding 1, dilation 1, groups 1; Cin = 1..256, Cout = 1..4; zeros_pad = 0: replicate padding, 1: zeros.
+ * x and dx [B, Cin, D, H, W], y and g_y [B, Cout, D, H, W], w and dw [Cout, Cin, 3, 3, 3] (nn.Conv3d's layout), bias and db [Cout]:
+ * all contiguous and 16-byte aligned.  With c(i) = clamp(i, 0, n - 1) per dimension in replicate mode (in zeros mode a tap outside
+ * the volume contributes nothing):
+ *   forward:   y[b,co,o]     = bias[co] + sum_ci sum_tap w[co,ci,tap] x[b,ci,c(o + tap - 1)]             (bias may be NULL: no bias)
+ *   backward:  dx[b,ci,i]    = sum_co sum_{(o,tap): c(o + tap - 1) = i} w[co,ci,tap] g_y[b,co,o]
+ *              dw[co,ci,tap] = sum_b sum_o g_y[b,co,o] x[b,ci,c(o + tap - 1)];   db[co] = sum_b sum_o g_y[b,co,o]
+ * The padded volume is never written.  All passes gather: every output element is written once, by one thread, from a sum whose terms
+ * and order depend on the shape alone; in replicate mode a border voxel of dx collects what its replicated copies received (up to 8
+ * padded positions at a corner, 27 when D = H = W = 1).  The forward is one launch.  dx, dw and db may each be NULL and only what is
+ * asked for is computed: dx is one launch that reads g_y and w only (no workspace; x may be NULL when dw is NULL); dw and db are two
+ * launches: the tiles of 32 x 8 x 8 voxels (W x H x D), in their linear order, are cut into at most 64 runs whose number and length
+ * depend on the shape alone, every run is summed to one RECORD [Cout, 27 Cin + 1] in the workspace, and the second launch adds the
+ * records in ascending order, in double.  split (0: chosen from the shape; 1..64: forced, a test aid; never more than the number of
+ * runs) is the number of workgroups that share the runs: it says which workgroup computes a record, never what the record is -- dw
+ * and db are the same bits for every split.
+ * workspace: 16-byte aligned, at least as many bytes as the size query returns for the same shape (0 for sizes outside the limits,
+ * else a multiple of 256); needed only when dw or db is asked for.
+ * MGS_ERR_INVALID_ARG before any launch: Cin outside 1..256; Cout outside 1..4; B or an extent below 1; D H W >= 2^31 (elements per
+ * (batch, channel) row), or B times the number of tiles above 2^31 - 1; zeros_pad other than 0 or 1; a NULL pointer where one is
+ * required (dx, dw and db all NULL included); a pointer not 16-byte aligned; split outside [0, 64].  MGS_ERR_WORKSPACE: fewer bytes
+ * than the query's.  Element offsets are 64-bit.
+ * No atomics, no workgroup waits for another, nothing to zero: bit-identical from run to run.  No host read, no allocation, no
+ * state: capturable into a HIP graph. */
+size_t mgs_narrow_conv3d_workspace_bytes(int64_t B, int Cin, int Cout, int64_t D, int64_t H, int64_t W);
+int mgs_narrow_conv3d_forward(int64_t B, int Cin, int Cout, int64_t D, int64_t H, int64_t W, int zeros_pad, const float* x,
+                              const float* w, const float* bias, float* y, mgs_stream_t stream);
+int mgs_narrow_conv3d_backward(int64_t B, int Cin, int Cout, int64_t D, int64_t H, int64_t W, int zeros_pad, const float* x,
+                               const float* g_y, const float* w, float* dx, float* dw, float* db, void* workspace,
+                               size_t workspace_bytes, int split, mgs_stream_t stream);
+
 /* Per-stage device timing (hipEvents on the caller's stream), enabled with
  * mgs_set_option("profile", 1) (render backward only) or 2 (every stage).  mgs_profile_read waits for the
  * recorded events, writes the summed milliseconds and launch counts per stage ([mgs_profile_num_stages()]),

@@ -12,6 +12,9 @@ CPU tensors take the torch composition above.
 `Conv3DBlock` and `Conv3DUpsampleBlock` have the reference's constructors, parameter names and initialisation; a reference
 state_dict loads with strict=True and the other way round.  The convolutions stay MIOpen's and the activations torch's: a block
 in replicate mode hands `F.conv3d(..., padding=0)` the volume this op padded, which is what nn.Conv3d computes in that mode.
+The one exception is a 3x3x3 block with at most 4 output channels (trans_decoder, perceiver_lang_io.py:322): where narrow_site()
+says so (NARROW overrides it) it goes through narrow_conv3d (narrow.py, csrc/mgs_narrow.hip), which folds the pad into its
+addressing, so that the input is not padded first.
 """
 import ctypes
 
@@ -20,9 +23,45 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib, _ops
+from .narrow import MAX_CIN as NARROW_MAX_CIN, MAX_COUT as NARROW_MAX_COUT, narrow_conv3d
 
 LRELU_SLOPE = 0.02
 MAX_SOURCES, MAX_SCALE, MAX_PAD = _lib.VOLUME_MAX_SOURCES, 8, 8
+
+# Whether a narrow-output 3x3x3 block goes through narrow_conv3d (csrc/mgs_narrow.hip).  NARROW: None = follow narrow_site();
+# True / False = every eligible block / none (tests, scripts/bench_narrow.py).
+NARROW = None
+NARROW_CHANNELS = (128, 1)   # the channel counts that were measured (trans_decoder's)
+NARROW_MIN_VOXELS = 25 ** 3  # D H W of the smallest measured winner, [1, 128 -> 1, 25^3] (None: no measured shape won all four pairs)
+
+
+def narrow_site(cin, cout, voxels):
+    """The routing rule of the narrow-output 3x3x3 block (voxels = D H W), from the measurement (scripts/bench_narrow.py ->
+    profiles/narrow_conv_bench.json), by encoder.fused_site()'s criterion: a shape is routed only where the op's third
+    quartile lay below the first quartile of the parent's path (resample_pad + F.conv3d(padding=0), at the faster of cudnn.benchmark
+    off and on) for forward AND forward + backward, eager AND graph-replayed.  Nothing else was measured, so nothing else is routed:
+    the threshold is the smallest winner's own size, at its own channel counts."""
+    if NARROW_MIN_VOXELS is None:
+        return False
+    return (cin, cout) == NARROW_CHANNELS and voxels >= NARROW_MIN_VOXELS
+
+
+def _narrow_routed(conv, x):
+    """Whether `conv` (a 3x3x3 nn.Conv3d of trans_decoder's kind) on x goes through the kernels."""
+    if NARROW is False or not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
+        return False
+    w, b = conv.weight, conv.bias
+    if x.dim() != 5 or x.numel() == 0 or w.dtype != torch.float32 or w.device != x.device:
+        return False
+    if b is not None and (b.dtype != torch.float32 or b.device != x.device):
+        return False
+    if conv.kernel_size != (3, 3, 3) or conv.stride != (1, 1, 1) or conv.padding != (1, 1, 1) or conv.dilation != (1, 1, 1):
+        return False
+    if conv.groups != 1 or conv.padding_mode not in ("replicate", "zeros") or x.size(1) != conv.in_channels:
+        return False
+    if conv.out_channels > NARROW_MAX_COUT or conv.in_channels > NARROW_MAX_CIN or x[0, 0].numel() >= 2 ** 31:
+        return False
+    return True if NARROW else narrow_site(conv.in_channels, conv.out_channels, x[0, 0].numel())
 
 def _in_place(t):
     """The tensor itself when the kernels can read it where it lies -- spatial dimensions contiguous, batch and channel strides
@@ -162,6 +201,10 @@ class Conv3DBlock(nn.Module):
 
     def forward(self, x):
         several = not isinstance(x, torch.Tensor)
+        if not several and _narrow_routed(self.conv3d, x):
+            c = self.conv3d
+            x = narrow_conv3d(x, c.weight, c.bias, c.padding_mode)
+            return self.activation(x) if self.activation is not None else x
         pad = self.fused_pad()
         if pad is None or (pad == 0 and not several):
             x = self.conv3d(torch.cat(list(x), 1) if several else x)

@@ -977,6 +977,44 @@ int mgs_narrow_conv3d_backward(int64_t B, int Cin, int Cout, int64_t D, int64_t 
                                const float* g_y, const float* w, float* dx, float* dw, float* db, void* workspace,
                                size_t workspace_bytes, int split, mgs_stream_t stream);
 
+/* ---- the Perceiver decoder's dense 3x3x3 / 5x5x5 convolutions with bias and leaky ReLU on the exact-f32 MFMA (SURVEY.md 2:
+ * agents/manigaussian_bc/perceiver_lang_io.py, up0 = Conv3DUpsampleBlock(256, 128, 5) and final = Conv3DBlock(256, 128, 3)) --
+ * additive exports, ABI v17 ----
+ * Kernel k x k x k with k = 3 or 5, stride 1, NO padding (the caller's volume already carries it), dilation 1, groups 1; Cin a
+ * multiple of 8 in 8..256, Cout a multiple of 32 in 32..256; every input extent at least k.  Do = Di - k + 1 and so on.
+ * x and dx [B, Cin, Di, Hi, Wi], y and g_y [B, Cout, Do, Ho, Wo], w and dw [Cout, Cin, k, k, k] (nn.Conv3d's layout), bias and db
+ * [Cout]: all contiguous and 16-byte aligned.  negative_slope < 0: no activation; >= 0: act(z) = z > 0 ? z : negative_slope z
+ * (0: ReLU).
+ *   forward:   y[b,co,o]     = act(bias[co] + sum_ci sum_tap w[co,ci,tap] x[b,ci,o + tap])                (bias may be NULL: no bias)
+ *   backward:  g'            = g_y (y > 0 ? 1 : negative_slope), or g_y without an activation (y may then be NULL)
+ *              dx[b,ci,i]    = sum_co sum_tap w[co,ci,tap] g'[b,co,i - tap]
+ *              dw[co,ci,tap] = sum_b sum_o g'[b,co,o] x[b,ci,o + tap];   db[co] = sum_b sum_o g'[b,co,o]
+ * All products run on v_mfma_f32_32x32x2_f32: k-ordered chains of fused multiply-adds in fp32.  The forward is two launches: the
+ * weights are rearranged into the workspace in the order the k loop consumes them, then one implicit GEMM.  dx, dw and db may each
+ * be NULL and only what is asked for is computed.  dx is three launches: g' is written into g_scratch, [B, Cout, Do + 2 (k - 1),
+ * Ho + 2 (k - 1), Wo + 2 (k - 1)] zero-padded (required when dx is asked for, else it may be NULL), the flipped and transposed
+ * weights into the workspace, and the forward's kernel runs on the two.  dw and db are two launches: the segments of up to 64 voxels
+ * of the output rows, in their linear order, are cut into runs whose number (at most 64, and at least 8 where there are as many
+ * segments) and length depend on the shape alone, every run is summed to one RECORD [Cout, Cin k^3 + 1] in the workspace (db, the
+ * last column, in double), and the second launch adds the records in ascending order, in double.  split (0: chosen from the shape;
+ * 1..64: forced, a test aid; never more than the number of runs) is the number of workgroups that share the runs: it says which
+ * workgroup computes a record, never what the record is -- dw and db are the same bits for every split.
+ * workspace: 16-byte aligned, at least as many bytes as the size query returns for the same shape (0 for shapes outside the limits,
+ * else a multiple of 256); needed by both calls.
+ * MGS_ERR_INVALID_ARG before any launch: k other than 3 or 5; Cin or Cout outside their limits or off their multiples; B below 1
+ * or above 65535; an extent below k; (Di + k - 1)(Hi + k - 1)(Wi + k - 1) >= 2^31 (the longest (batch, channel) row there is);
+ * more than 2^31 - 1 row segments; a NaN slope; a NULL pointer where one is required (dx, dw and db all NULL included); a pointer
+ * not 16-byte aligned; split outside [0, 64].  MGS_ERR_WORKSPACE: fewer bytes than the query's.  Element offsets are 64-bit.
+ * No atomics, no workgroup waits for another, nothing to zero: bit-identical from run to run.  No host read, no allocation, no
+ * state: capturable into a HIP graph. */
+size_t mgs_dense_conv3d_workspace_bytes(int64_t B, int Cin, int Cout, int k, int64_t Di, int64_t Hi, int64_t Wi);
+int mgs_dense_conv3d_forward(int64_t B, int Cin, int Cout, int k, int64_t Di, int64_t Hi, int64_t Wi, float negative_slope,
+                             const float* x, const float* w, const float* bias, float* y, void* workspace, size_t workspace_bytes,
+                             mgs_stream_t stream);
+int mgs_dense_conv3d_backward(int64_t B, int Cin, int Cout, int k, int64_t Di, int64_t Hi, int64_t Wi, float negative_slope,
+                              const float* x, const float* y, const float* g_y, const float* w, float* dx, float* dw, float* db,
+                              float* g_scratch, void* workspace, size_t workspace_bytes, int split, mgs_stream_t stream);
+
 /* Per-stage device timing (hipEvents on the caller's stream), enabled with
  * mgs_set_option("profile", 1) (render backward only) or 2 (every stage).  mgs_profile_read waits for the
  * recorded events, writes the summed milliseconds and launch counts per stage ([mgs_profile_num_stages()]),

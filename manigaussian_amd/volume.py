@@ -14,7 +14,9 @@ state_dict loads with strict=True and the other way round.  The convolutions sta
 in replicate mode hands `F.conv3d(..., padding=0)` the volume this op padded, which is what nn.Conv3d computes in that mode.
 The one exception is a 3x3x3 block with at most 4 output channels (trans_decoder, perceiver_lang_io.py:322): where narrow_site()
 says so (NARROW overrides it) it goes through narrow_conv3d (narrow.py, csrc/mgs_narrow.hip), which folds the pad into its
-addressing, so that the input is not padded first.
+addressing, so that the input is not padded first.  A dense 3x3x3 or 5x5x5 block at channel counts dense_conv3d takes (up0's two
+blocks and final) runs its convolution, bias and ReLU / leaky ReLU as one op on the volume this module padded (dense.py,
+csrc/mgs_dense.hip) where dense_site() says so (DENSE overrides it).
 """
 import ctypes
 
@@ -23,6 +25,8 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib, _ops
+from . import dense as _dense
+from .dense import dense_conv3d
 from .narrow import MAX_CIN as NARROW_MAX_CIN, MAX_COUT as NARROW_MAX_COUT, narrow_conv3d
 
 LRELU_SLOPE = 0.02
@@ -62,6 +66,55 @@ def _narrow_routed(conv, x):
     if conv.out_channels > NARROW_MAX_COUT or conv.in_channels > NARROW_MAX_CIN or x[0, 0].numel() >= 2 ** 31:
         return False
     return True if NARROW else narrow_site(conv.in_channels, conv.out_channels, x[0, 0].numel())
+
+
+# Whether a dense 3x3x3 / 5x5x5 block's convolution (on the padded volume) goes through dense_conv3d (csrc/mgs_dense.hip).  DENSE:
+# None = follow dense_site(); True / False = every eligible block / none (tests, scripts/bench_dense.py).
+DENSE = None
+# (cin, cout, k) -> output voxels of the smallest measured winner at these channel counts (scripts/bench_dense.py ->
+# profiles/dense_conv_bench.json); a triple that was not measured, or that won nowhere, is not here
+DENSE_MIN_VOXELS = {}
+
+
+def dense_site(cin, cout, k, voxels):
+    """The routing rule of the dense blocks (voxels = output D H W), from the measurement (scripts/bench_dense.py ->
+    profiles/dense_conv_bench.json), by encoder.fused_site()'s criterion: a shape is routed only where the op's third
+    quartile lay below the first quartile of torch's F.leaky_relu(F.conv3d(...)) (at the faster of cudnn.benchmark off and on) for
+    forward AND forward + backward, eager AND graph-replayed.  Only measured (cin, cout, k) triples are routed, each from its
+    smallest measured winner's size up."""
+    least = DENSE_MIN_VOXELS.get((cin, cout, k))
+    return least is not None and voxels >= least
+
+
+def _dense_slope(activation):
+    """(whether the op can fuse the block's activation, the slope it takes)"""
+    if activation is None:
+        return True, None
+    if type(activation) is nn.LeakyReLU and activation.negative_slope >= 0:
+        return True, float(activation.negative_slope)
+    if type(activation) is nn.ReLU:
+        return True, 0.0
+    return False, None
+
+
+def _dense_routed(conv, x):
+    """Whether `conv` on x, the volume that already carries its padding, goes through the kernels."""
+    if DENSE is False or not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
+        return False
+    w, b = conv.weight, conv.bias
+    if x.dim() != 5 or x.numel() == 0 or w.dtype != torch.float32 or w.device != x.device:
+        return False
+    if b is not None and (b.dtype != torch.float32 or b.device != x.device):
+        return False
+    k = conv.kernel_size
+    if len(set(k)) != 1 or conv.stride != (1, 1, 1) or conv.dilation != (1, 1, 1) or conv.groups != 1 or x.size(1) != conv.in_channels:
+        return False
+    if x.size(0) > 65535 or not _dense.eligible(conv.in_channels, conv.out_channels, k[0], tuple(x.shape[2:])):
+        return False
+    if DENSE:
+        return True
+    return dense_site(conv.in_channels, conv.out_channels, k[0], (x.size(2) - k[0] + 1) * (x.size(3) - k[0] + 1) * (x.size(4) - k[0] + 1))
+
 
 def _in_place(t):
     """The tensor itself when the kernels can read it where it lies -- spatial dimensions contiguous, batch and channel strides
@@ -196,6 +249,10 @@ class Conv3DBlock(nn.Module):
     def forward_padded(self, x):
         """The block on a volume that already carries its padding."""
         c = self.conv3d
+        if _dense_routed(c, x):
+            fused, slope = _dense_slope(self.activation)
+            x = dense_conv3d(x, c.weight, c.bias, slope)
+            return x if fused else self.activation(x)
         x = F.conv3d(x, c.weight, c.bias, c.stride, 0, c.dilation, c.groups)
         return self.activation(x) if self.activation is not None else x
 
@@ -206,6 +263,8 @@ class Conv3DBlock(nn.Module):
             x = narrow_conv3d(x, c.weight, c.bias, c.padding_mode)
             return self.activation(x) if self.activation is not None else x
         pad = self.fused_pad()
+        if pad == 0 and not several and _dense_routed(self.conv3d, x):
+            return self.forward_padded(x)
         if pad is None or (pad == 0 and not several):
             x = self.conv3d(torch.cat(list(x), 1) if several else x)
             return self.activation(x) if self.activation is not None else x

@@ -1,6 +1,6 @@
 """The launch layer: what an op wrapper needs between torch and the C ABI of libmgsplat.so -- the current stream, the
-current device, a workspace, a pointer, and the call itself with its error check.  Every op module uses these; none keeps
-a copy of its own.
+current device, a workspace, a pointer, a tensor the kernels can read in place, the float32-on-device check of the operands, and
+the call itself with its error check.  Every op module uses these; none keeps a copy of its own.
 """
 import ctypes
 
@@ -38,6 +38,24 @@ class on_device:
 
 def ptr(t):
     return None if (t is None or t.numel() == 0) else t.data_ptr()
+
+
+def readable(t):
+    """The tensor itself when the kernels can read it in place (contiguous, 16-byte aligned), else one contiguous copy."""
+    if t.is_contiguous() and t.data_ptr() % 16 == 0:
+        return t
+    return t.contiguous() if not t.is_contiguous() else t.clone()
+
+
+def need_float32(op, optional=(), **tensors):
+    """RuntimeError unless every named operand of `op` is a float32 tensor on a HIP device; an operand named in `optional` may be
+    None."""
+    for name, t in tensors.items():
+        if t is None and name in optional:
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+            raise RuntimeError(f"{op} needs float32 tensors on a HIP device ({name} is "
+                               f"{getattr(t, 'dtype', type(t))} on {getattr(t, 'device', 'the host')}); there is no CPU path")
 
 
 def call(name, dev, *args):

@@ -15,16 +15,9 @@ workgroups.  No host read, no allocation beyond the outputs and the device's sha
 """
 import torch
 
-from . import _lib, _ops
+from . import _conv, _lib, _ops
 
 MAX_C = 64
-
-
-def _readable(t):
-    """The tensor itself when the kernels can read it in place (contiguous, 16-byte aligned), else one contiguous copy."""
-    if t.is_contiguous() and t.data_ptr() % 16 == 0:
-        return t
-    return t.contiguous() if not t.is_contiguous() else t.clone()
 
 
 def _forward(x, w, y, B, cin, cout, ext, stride):
@@ -49,7 +42,7 @@ def _out_extent(i, stride):
 class _Conv3d(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, stride, split):
-        x, weight = _readable(x), _readable(weight)
+        x, weight = _ops.readable(x), _ops.readable(weight)
         B, cin = x.shape[:2]
         cout = weight.size(0)
         ext = tuple(x.shape[2:])
@@ -67,7 +60,7 @@ class _Conv3d(torch.autograd.Function):
         ext = tuple(x.shape[2:])
         dx = dw = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            g = _readable(g)
+            g = _ops.readable(g)
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             _backward_data(g, weight, dx, B, cin, cout, ext, ctx.stride)
@@ -83,7 +76,7 @@ class _ConvTranspose3d(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, output_padding, split):
-        x, weight = _readable(x), _readable(weight)
+        x, weight = _ops.readable(x), _ops.readable(weight)
         B, cout = x.shape[:2]
         cin = weight.size(1)
         ext = tuple(2 * i - 1 + output_padding for i in x.shape[2:])
@@ -100,7 +93,7 @@ class _ConvTranspose3d(torch.autograd.Function):
         cin = weight.size(1)
         dx = dw = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            g = _readable(g)
+            g = _ops.readable(g)
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             _forward(g, weight, dx, B, cin, cout, ctx.ext, 2)
@@ -111,20 +104,11 @@ class _ConvTranspose3d(torch.autograd.Function):
 
 
 def _check(op, x, weight, channel_dim):
-    for name, t in (("x", x), ("weight", weight)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-            raise RuntimeError(f"{op} needs float32 tensors on a HIP device ({name} is "
-                               f"{getattr(t, 'dtype', type(t))} on {getattr(t, 'device', 'the host')}); there is no CPU path")
-    if x.dim() != 5 or x.numel() == 0:
-        raise ValueError(f"expected x [B,C,D,H,W] with no empty dimension, got {tuple(x.shape)}")
-    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or weight.size(channel_dim) != x.size(1):
-        raise ValueError(f"weight {tuple(weight.shape)} is not a 3x3x3 kernel over the {x.size(1)} channels of x")
-    if weight.device != x.device:
-        raise ValueError(f"weight must be on {x.device}")
+    _ops.need_float32(op, x=x, weight=weight)
+    _conv.check_shapes(x, weight, (3,), channel_dim)
     if not (1 <= weight.size(0) <= MAX_C and 1 <= weight.size(1) <= MAX_C):
         raise ValueError(f"weight {tuple(weight.shape)}: 1 to {MAX_C} channels on either side")
-    if x[0, 0].numel() >= 2 ** 31:
-        raise ValueError(f"x {tuple(x.shape)}: a (batch, channel) row must hold fewer than 2^31 elements")
+    _conv.check_rows(x)
 
 
 def _conv3d(x, weight, stride=1, split=0):

@@ -281,6 +281,18 @@ int launch_done(const char* fn);          // after the launches: MGS_OK, or "<fn
 bool misaligned16(const void* p);         // p is not 16-byte aligned
 int workspace_short(const char* fn, size_t have, size_t need);  // MGS_OK, or the message and MGS_ERR_WORKSPACE when have < need
 
+// the partial records of the Conv3d families' weight | bias gradients (mgs_records.hip)
+constexpr int MAX_REC = 64;               // most records of one gradient
+struct Runs { int64_t n, per; };          // n runs of `per` items (the last one may be shorter)
+Runs cut_runs(int64_t items, int64_t most);   // items >= 1 in linear order cut into at most `most` >= 1 runs: a function of the two alone
+int split_check(const char* fn, int split);   // MGS_OK, or the message and MGS_ERR_INVALID_ARG unless 0 <= split <= MAX_REC
+int64_t split_clamp(int split, int64_t dflt, int64_t nrec);   // the workgroups that share nrec runs: split, or dflt where it is 0
+bool row_too_long(int64_t d, int64_t h, int64_t w);           // a row of d x h x w elements cannot be indexed in 32 bits
+// MGS_OK, or the message and its code: the records' workspace is NULL, misaligned or shorter than `need`
+int records_workspace(const char* fn, const void* workspace, size_t have, size_t need);
+// records [nrec, rows, cols] -> dw [rows, wcols] (wcols = cols or cols - 1), db [rows] from column cols - 1; dw or db may be nullptr
+void launch_records_merge(int64_t nrec, int rows, int cols, int wcols, const float* records, float* dw, float* db, hipStream_t s);
+
 constexpr int MAX_VIEWS = 16;
 struct ViewCam {  // per-view camera of a multi-view batch
   float tanfovx, tanfovy, focal_x, focal_y;

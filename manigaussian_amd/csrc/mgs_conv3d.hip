@@ -20,7 +20,7 @@
 // input channels: per dimension tap 1 feeds the even voxel from g[m], taps 0 and 2 feed the odd one from g[m+1] and g[m], so each of
 // the 27 taps is used exactly once per block -- the 1, 2, 4 or 8 terms of the eight parity classes -- from 8 staged values of g.
 //
-// Backward-weight (cv_bwd_weight_kernel<S>, cv_merge_kernel).  The output tiles of the forward, in their linear order, are cut into
+// Backward-weight (cv_bwd_weight_kernel<S>; merge: mgs_records.hip).  The output tiles of the forward, in their linear order, are cut into
 // nrec <= 64 runs of tpr tiles; nrec and tpr depend on the shape alone.  A workgroup takes one input channel and 4 output channels
 // and, per run, keeps 4 x 27 accumulators per thread over the run's tiles (x from the staged halo tile, g from memory, one voxel
 // column per thread), then adds them up over its 256 threads in a fixed order into the run's RECORD [Cout, Cin, 27] in the workspace.
@@ -35,7 +35,6 @@ namespace mgs {
 constexpr int CV_THREADS = 256;
 constexpr int CV_TW = 32, CV_TH = 8;       // an output tile's lanes along W and rows along H
 constexpr int CV_MAX_C = 64;
-constexpr int CV_MAX_REC = 64;             // most partial records of the weight gradient
 constexpr int CV_TARGET_BLOCKS = 2048;
 constexpr int CV_BW_COG = 4;               // output channels per workgroup of the weight gradient
 constexpr int CV_TAPS = 27;
@@ -320,15 +319,6 @@ __global__ __launch_bounds__(CV_THREADS, 2) void cv_bwd_weight_kernel(CvGeom g, 
   }
 }
 
-__global__ __launch_bounds__(CV_THREADS) void cv_merge_kernel(uint32_t nrec, uint32_t n, const float* __restrict__ records,
-                                                              float* __restrict__ dw) {
-  const uint32_t e = blockIdx.x * CV_THREADS + threadIdx.x;
-  if (e >= n) return;
-  double s = 0.0;
-  for (uint32_t r = 0; r < nrec; ++r) s += (double)records[(size_t)r * n + e];
-  dw[e] = (float)s;
-}
-
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 struct CvShape {
   int64_t B;
@@ -339,15 +329,13 @@ struct CvShape {
   int64_t nrec, tpr;            // the weight gradient's records
 };
 
-// sizes inside the limits -> *sh; else false and the reason in *why (why may be nullptr)
+// sizes inside the limits -> *sh; else false and the reason in *why
 static bool cv_shape(int64_t B, int Cin, int Cout, int64_t D, int64_t H, int64_t W, int stride, CvShape* sh, const char** why) {
-  const char* unused;
-  if (!why) why = &unused;
   if (Cin < 1 || Cin > CV_MAX_C || Cout < 1 || Cout > CV_MAX_C) { *why = "channel counts must be 1 to 64"; return false; }
   if (stride != 1 && stride != 2) { *why = "stride must be 1 or 2"; return false; }
   if (B < 1 || D < 1 || H < 1 || W < 1) { *why = "B and every extent must be at least 1"; return false; }
+  if (row_too_long(D, H, W)) { *why = "a (batch, channel) row must hold fewer than 2^31 elements"; return false; }
   const int64_t lim = 0x7fffffff;
-  if (D > lim || H > lim || W > lim || D * H > lim || D * H * W > lim) { *why = "a (batch, channel) row must hold fewer than 2^31 elements"; return false; }
   sh->B = B; sh->Cin = Cin; sh->Cout = Cout; sh->S = stride;
   sh->I[0] = D; sh->I[1] = H; sh->I[2] = W;
   for (int k = 0; k < 3; ++k) sh->O[k] = (sh->I[k] - 1) / stride + 1;
@@ -362,9 +350,8 @@ static bool cv_shape(int64_t B, int Cin, int Cout, int64_t D, int64_t H, int64_t
   const int64_t finest = ((D + 1) / 2 + 1) * ((H + 3) / 4 + 1) * ((W + 31) / 32 + 1);
   if (B > lim / (per > finest ? per : finest)) { *why = "B times the number of tiles exceeds 2^31 - 1"; return false; }
   sh->ntiles = B * per;
-  const int64_t want = sh->ntiles < CV_MAX_REC ? sh->ntiles : CV_MAX_REC;
-  sh->tpr = (sh->ntiles + want - 1) / want;
-  sh->nrec = (sh->ntiles + sh->tpr - 1) / sh->tpr;
+  const Runs runs = cut_runs(sh->ntiles, MAX_REC);
+  sh->nrec = runs.n; sh->tpr = runs.per;
   return true;
 }
 
@@ -402,7 +389,8 @@ extern "C" {
 
 size_t mgs_conv3d_workspace_bytes(int64_t B, int Cin, int Cout, int64_t D, int64_t H, int64_t W, int stride) {
   CvShape sh;
-  if (!cv_shape(B, Cin, Cout, D, H, W, stride, &sh, nullptr)) return 0;
+  const char* why;
+  if (!cv_shape(B, Cin, Cout, D, H, W, stride, &sh, &why)) return 0;
   return align_up((size_t)sh.nrec * (size_t)Cout * (size_t)Cin * CV_TAPS * sizeof(float)) + ALIGN;
 }
 
@@ -450,18 +438,13 @@ int mgs_conv3d_backward_weight(int64_t B, int Cin, int Cout, int64_t D, int64_t 
   const char* fn = "conv3d_backward_weight";
   CvShape sh;
   if (int rc = cv_check(fn, B, Cin, Cout, D, H, W, stride, &sh)) return rc;
-  if (split < 0 || split > CV_MAX_REC) {
-    set_error("%s: split = %d (0: chosen by the library, at most %d)", fn, split, CV_MAX_REC);
-    return MGS_ERR_INVALID_ARG;
-  }
+  if (int rc = split_check(fn, split)) return rc;
   if (int rc = cv_pointers(fn, x, g_y, dw, "x, g_y or dw")) return rc;
-  if (!workspace || misaligned16(workspace)) { set_error("%s: NULL or misaligned workspace", fn); return MGS_ERR_INVALID_ARG; }
-  if (int rc = workspace_short(fn, workspace_bytes, mgs_conv3d_workspace_bytes(B, Cin, Cout, D, H, W, stride))) return rc;
+  if (int rc = records_workspace(fn, workspace, workspace_bytes, mgs_conv3d_workspace_bytes(B, Cin, Cout, D, H, W, stride))) return rc;
   hipStream_t s = (hipStream_t)stream;
   const CvGeom g = cv_geom(sh, Cin, Cout);
   const int64_t groups = (int64_t)((Cout + CV_BW_COG - 1) / CV_BW_COG) * Cin;
-  int64_t wgs = split ? split : (CV_TARGET_BLOCKS + groups - 1) / groups;
-  wgs = wgs < 1 ? 1 : (wgs > sh.nrec ? sh.nrec : wgs);
+  const int64_t wgs = split_clamp(split, (CV_TARGET_BLOCKS + groups - 1) / groups, sh.nrec);
   float* records = reinterpret_cast<float*>(workspace);
   const dim3 grid((unsigned)wgs, (unsigned)((Cout + CV_BW_COG - 1) / CV_BW_COG), (unsigned)Cin);
   if (stride == 1)
@@ -470,8 +453,7 @@ int mgs_conv3d_backward_weight(int64_t B, int Cin, int Cout, int64_t D, int64_t 
   else
     hipLaunchKernelGGL((cv_bwd_weight_kernel<2>), grid, dim3(CV_THREADS), 0, s, g, (uint32_t)sh.nrec, (uint32_t)sh.tpr,
                        (uint32_t)sh.ntiles, x, g_y, records);
-  const uint32_t n = (uint32_t)(Cout * Cin * CV_TAPS);
-  hipLaunchKernelGGL(cv_merge_kernel, dim3((n + CV_THREADS - 1) / CV_THREADS), dim3(CV_THREADS), 0, s, (uint32_t)sh.nrec, n, records, dw);
+  launch_records_merge(sh.nrec, Cout, Cin * CV_TAPS, Cin * CV_TAPS, records, dw, nullptr, s);
   return launch_done(fn);
 }
 

@@ -28,12 +28,12 @@
 // launch writes the flipped, channel-transposed weights, and the forward kernel on those two -- Cout input channels, Cin output
 // channels, no bias, no activation -- is dx.  No border case reaches the hot loop.
 //
-// Backward-weight and -bias (dc_bwd_weight_kernel, dc_merge_kernel).  C [Cout x (ci, tap)] = G' [Cout x voxels] X~ [voxels x (ci,
+// Backward-weight and -bias (dc_bwd_weight_kernel; merge: mgs_records.hip).  C [Cout x (ci, tap)] = G' [Cout x voxels] X~ [voxels x (ci,
 // tap)]: k is the voxel index, which runs along memory in both operands, so both go through LDS.  A k-slab is a SEGMENT of up to
 // DC_SEG = 64 voxels of one output row: g' (masked on the way in) lies as 128 rows of 65 floats and is read across the channels;
 // of x the k^2 halo rows of the N-tile's channels lie as rows of DC_SEG + k - 1 floats and a lane reads them at its column's own tap
 // offset, decoded once.  An N-tile is DC_WN = 128 columns: 4 channels x 27 taps padded to 32 (k = 3) or 1 channel x 125 taps padded to
-// 128 (k = 5).  The segments, in their linear order, are cut into nrec <= DC_MAX_REC runs whose number and length depend on the
+// 128 (k = 5).  The segments, in their linear order, are cut into nrec <= MAX_REC runs whose number and length depend on the
 // shape alone; a run's sums go to its RECORD [Cout, Cin k^3 + 1] in the workspace (the last column, db, by the workgroups of the
 // first N-tile, summed in double), and the merge launch adds the records in ascending order in double.  `split` is the number of
 // workgroups that share an N-tile's runs: it decides who computes a record, never what it holds.
@@ -54,7 +54,6 @@ constexpr int DC_WROW = DC_NT + 32;   // floats of a slab row in LDS
 constexpr int DC_SEG = 64;        // weight gradient: most voxels of an output row per k-slab
 constexpr int DC_GROW = DC_SEG + 1;   // floats of a row of g' in LDS
 constexpr int DC_WN = 128;        // weight gradient: columns of an N-tile
-constexpr int DC_MAX_REC = 64;    // most partial records of dw | db
 constexpr size_t DC_REC_BYTES = (size_t)128 << 20;   // ... and as many as fit these bytes (at least 8)
 constexpr int DC_MIN_C = 8, DC_MAX_C = 256;
 
@@ -338,19 +337,6 @@ __global__ __launch_bounds__(DC_THREADS, 2) void dc_bwd_weight_kernel(DcWGeom g,
   }
 }
 
-// records [nrec, Cout, cols] -> dw [Cout, cols - 1], db [Cout] (either may be nullptr), in ascending order in double
-__global__ __launch_bounds__(DC_THREADS) void dc_merge_kernel(uint32_t nrec, uint32_t cols, uint32_t total, const float* __restrict__ records,
-                                                              float* __restrict__ dw, float* __restrict__ db) {
-  const uint32_t e = blockIdx.x * (uint32_t)DC_THREADS + threadIdx.x;
-  if (e >= total) return;
-  const uint32_t co = e / cols, c = e - co * cols;
-  if (c < cols - 1 ? dw == nullptr : db == nullptr) return;
-  double s = 0.0;
-  for (uint32_t r = 0; r < nrec; ++r) s += (double)records[(size_t)r * total + e];
-  if (c < cols - 1) dw[(size_t)co * (cols - 1) + c] = (float)s;
-  else db[co] = (float)s;
-}
-
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
 struct DcShape {
   int64_t B, Di, Hi, Wi, Do, Ho, Wo, vin, vout, vpad;
@@ -363,17 +349,14 @@ struct DcShape {
 static int dc_pad_to(int c) { return (c + DC_NT - 1) / DC_NT * DC_NT; }
 
 static bool dc_shape(int64_t B, int Cin, int Cout, int K, int64_t Di, int64_t Hi, int64_t Wi, DcShape* sh, const char** why) {
-  const char* unused;
-  if (!why) why = &unused;
   if (K != 3 && K != 5) { *why = "k must be 3 or 5"; return false; }
   if (Cin < DC_MIN_C || Cin > DC_MAX_C || Cin % 8) { *why = "Cin must be a multiple of 8 in 8 to 256"; return false; }
   if (Cout < 32 || Cout > DC_MAX_C || Cout % 32) { *why = "Cout must be a multiple of 32 in 32 to 256"; return false; }
   if (B < 1) { *why = "B must be at least 1"; return false; }
   if (Di < K || Hi < K || Wi < K) { *why = "every extent must be at least k"; return false; }
-  const int64_t lim = 0x7fffffff;
   // (backward-data pads the output gradient to extents of Di + k - 1: that row is the longest one there is)
   const int64_t Dp = Di + K - 1, Hp = Hi + K - 1, Wp = Wi + K - 1;
-  if (Dp > lim || Hp > lim || Wp > lim || Dp * Hp > lim || Dp * Hp * Wp > lim) {
+  if (row_too_long(Dp, Hp, Wp)) {
     *why = "a (batch, channel) row, padded by k - 1, must hold fewer than 2^31 elements";
     return false;
   }
@@ -384,14 +367,13 @@ static bool dc_shape(int64_t B, int Cin, int Cout, int K, int64_t Di, int64_t Hi
   sh->mtiles = (sh->vout + DC_MT - 1) / DC_MT;
   sh->mtiles_dx = (sh->vin + DC_MT - 1) / DC_MT;
   sh->spr_row = (sh->Wo + DC_SEG - 1) / DC_SEG;
-  if (B * sh->Do > lim / (sh->Ho * sh->spr_row)) { *why = "the number of row segments (tiles of the weight gradient) exceeds 2^31 - 1"; return false; }
+  if (B * sh->Do > (int64_t)0x7fffffff / (sh->Ho * sh->spr_row)) { *why = "the number of row segments (tiles of the weight gradient) exceeds 2^31 - 1"; return false; }
   sh->nseg = B * sh->Do * sh->Ho * sh->spr_row;
   sh->rec_bytes = (size_t)Cout * ((size_t)Cin * sh->K3 + 1) * sizeof(float);
   int64_t want = (int64_t)(DC_REC_BYTES / sh->rec_bytes);
-  want = want < 8 ? 8 : (want > DC_MAX_REC ? DC_MAX_REC : want);
-  want = want > sh->nseg ? sh->nseg : want;
-  sh->spr = (sh->nseg + want - 1) / want;
-  sh->nrec = (sh->nseg + sh->spr - 1) / sh->spr;
+  want = want < 8 ? 8 : (want > MAX_REC ? MAX_REC : want);
+  const Runs runs = cut_runs(sh->nseg, want);
+  sh->nrec = runs.n; sh->spr = runs.per;
   const size_t fwd = (size_t)Cin * sh->K3 * dc_pad_to(Cout), bwd = (size_t)Cout * sh->K3 * dc_pad_to(Cin);
   sh->wp_bytes = align_up((fwd > bwd ? fwd : bwd) * sizeof(float));
   return true;
@@ -436,7 +418,8 @@ extern "C" {
 
 size_t mgs_dense_conv3d_workspace_bytes(int64_t B, int Cin, int Cout, int k, int64_t Di, int64_t Hi, int64_t Wi) {
   DcShape sh;
-  if (!dc_shape(B, Cin, Cout, k, Di, Hi, Wi, &sh, nullptr)) return 0;
+  const char* why;
+  if (!dc_shape(B, Cin, Cout, k, Di, Hi, Wi, &sh, &why)) return 0;
   return sh.wp_bytes + align_up((size_t)sh.nrec * sh.rec_bytes) + ALIGN;
 }
 
@@ -464,10 +447,7 @@ int mgs_dense_conv3d_backward(int64_t B, int Cin, int Cout, int k, int64_t Di, i
   const char* fn = "dense_conv3d_backward";
   DcShape sh;
   if (int rc = dc_check(fn, B, Cin, Cout, k, Di, Hi, Wi, negative_slope, &sh)) return rc;
-  if (split < 0 || split > DC_MAX_REC) {
-    set_error("%s: split = %d (0: chosen by the library, at most %d)", fn, split, DC_MAX_REC);
-    return MGS_ERR_INVALID_ARG;
-  }
+  if (int rc = split_check(fn, split)) return rc;
   const int act = negative_slope >= 0.f;
   if (!dx && !dw && !db) { set_error("%s: NULL dx, dw and db: no gradient is asked for", fn); return MGS_ERR_INVALID_ARG; }
   if (!g_y || (act && !y) || (dx && (!w || !g_scratch)) || (dw && !x) || !workspace) {
@@ -499,15 +479,12 @@ int mgs_dense_conv3d_backward(int64_t B, int Cin, int Cout, int k, int64_t Di, i
     g.spr_row = (int)sh.spr_row; g.nseg = (uint32_t)sh.nseg; g.nrec = (uint32_t)sh.nrec; g.spr = (uint32_t)sh.spr;
     g.vin = sh.vin; g.vout = sh.vout;
     g.act = act; g.want_dw = dw != nullptr; g.slope = negative_slope;
-    int64_t wgs = split ? split : sh.nrec;
-    wgs = wgs > sh.nrec ? sh.nrec : wgs;
+    const int64_t wgs = split_clamp(split, sh.nrec, sh.nrec);
     const int ch = k == 3 ? 4 : 1;
     const dim3 grid((unsigned)(g.want_dw ? Cin / ch : 1), (unsigned)(dc_pad_to(Cout) / DC_NT), (unsigned)wgs);
     if (k == 3) hipLaunchKernelGGL((dc_bwd_weight_kernel<3>), grid, dim3(DC_THREADS), 0, s, g, x, y, g_y, records);
     else hipLaunchKernelGGL((dc_bwd_weight_kernel<5>), grid, dim3(DC_THREADS), 0, s, g, x, y, g_y, records);
-    const uint32_t cols = (uint32_t)(Cin * sh.K3 + 1), total = (uint32_t)Cout * cols;
-    hipLaunchKernelGGL(dc_merge_kernel, dim3((total + DC_THREADS - 1) / DC_THREADS), dim3(DC_THREADS), 0, s, (uint32_t)sh.nrec, cols, total,
-                       records, dw, db);
+    launch_records_merge(sh.nrec, Cout, Cin * sh.K3 + 1, Cin * sh.K3, records, dw, db, s);
   }
   return launch_done(fn);
 }

@@ -29,7 +29,7 @@
 // row, along W the centre value to its neighbour in the same way -- a select per value, only in tiles that touch such a border --
 // and along D, where the border is uniform across the wave, the centre plane is run through the third set of weights as well.
 //
-// Backward-weight and -bias (nc_bwd_weight_kernel, nc_merge_kernel).  The tiles, in their linear order, are cut into nrec <= 64 runs
+// Backward-weight and -bias (nc_bwd_weight_kernel; merge: mgs_records.hip).  The tiles, in their linear order, are cut into nrec <= 64 runs
 // of tpr tiles; nrec and tpr depend on the shape alone.  A workgroup of one group takes two input channels at Cout = 1, else one (their
 // sums have to fit the registers) and, per run, keeps 27 Cout sums per channel and Cout for db per thread over the run's tiles: per
 // tile the box offsets and g of the thread's own 16 voxels are worked out and read once, then the channels' halo boxes of x go
@@ -44,7 +44,6 @@
 namespace mgs {
 
 constexpr int NC_MAX_CIN = 256, NC_MAX_COUT = 4;
-constexpr int NC_MAX_REC = 64;                      // most partial records of dw | db
 constexpr int NC_TW = 32, NC_TH = 8, NC_TD = 8;     // a tile
 constexpr int NC_GROUP = 128;                       // threads on a tile: 8 (W) x 8 (H) x 2 (D) register blocks of 4 (D) x 4 (W)
 constexpr int NC_EW = NC_TW + 2, NC_EH = NC_TH + 2, NC_ED = NC_TD + 2;
@@ -467,19 +466,6 @@ __global__ __launch_bounds__(NC_GROUP, 2) void nc_bwd_weight_kernel(NcGeom g, ui
   }
 }
 
-// records [nrec, Cout, 27 Cin + 1] -> dw [Cout, Cin, 27], db [Cout] (either may be nullptr), in ascending order in double
-__global__ __launch_bounds__(256) void nc_merge_kernel(uint32_t nrec, uint32_t cols, uint32_t total, const float* __restrict__ records,
-                                                       float* __restrict__ dw, float* __restrict__ db) {
-  const uint32_t e = blockIdx.x * 256u + threadIdx.x;
-  if (e >= total) return;
-  const uint32_t co = e / cols, c = e - co * cols;
-  if (c < cols - 1 ? dw == nullptr : db == nullptr) return;
-  double s = 0.0;
-  for (uint32_t r = 0; r < nrec; ++r) s += (double)records[(size_t)r * total + e];
-  if (c < cols - 1) dw[(size_t)co * (cols - 1) + c] = (float)s;
-  else db[co] = (float)s;
-}
-
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 struct NcShape {
   int64_t B, D, H, W, vol;
@@ -489,13 +475,11 @@ struct NcShape {
 };
 
 static bool nc_shape(int64_t B, int Cin, int Cout, int64_t D, int64_t H, int64_t W, NcShape* sh, const char** why) {
-  const char* unused;
-  if (!why) why = &unused;
   if (Cin < 1 || Cin > NC_MAX_CIN) { *why = "Cin must be 1 to 256"; return false; }
   if (Cout < 1 || Cout > NC_MAX_COUT) { *why = "Cout must be 1 to 4"; return false; }
   if (B < 1 || D < 1 || H < 1 || W < 1) { *why = "B and every extent must be at least 1"; return false; }
+  if (row_too_long(D, H, W)) { *why = "a (batch, channel) row must hold fewer than 2^31 elements"; return false; }
   const int64_t lim = 0x7fffffff;
-  if (D > lim || H > lim || W > lim || D * H > lim || D * H * W > lim) { *why = "a (batch, channel) row must hold fewer than 2^31 elements"; return false; }
   sh->B = B; sh->D = D; sh->H = H; sh->W = W; sh->vol = D * H * W; sh->Cin = Cin; sh->Cout = Cout;
   sh->tiles[0] = (D + NC_TD - 1) / NC_TD;
   sh->tiles[1] = (H + NC_TH - 1) / NC_TH;
@@ -503,9 +487,8 @@ static bool nc_shape(int64_t B, int Cin, int Cout, int64_t D, int64_t H, int64_t
   const int64_t per = sh->tiles[0] * sh->tiles[1] * sh->tiles[2];
   if (B > lim / per) { *why = "B times the number of tiles exceeds 2^31 - 1"; return false; }
   sh->ntiles = B * per;
-  const int64_t want = sh->ntiles < NC_MAX_REC ? sh->ntiles : NC_MAX_REC;
-  sh->tpr = (sh->ntiles + want - 1) / want;
-  sh->nrec = (sh->ntiles + sh->tpr - 1) / sh->tpr;
+  const Runs runs = cut_runs(sh->ntiles, MAX_REC);
+  sh->nrec = runs.n; sh->tpr = runs.per;
   return true;
 }
 
@@ -553,7 +536,8 @@ extern "C" {
 
 size_t mgs_narrow_conv3d_workspace_bytes(int64_t B, int Cin, int Cout, int64_t D, int64_t H, int64_t W) {
   NcShape sh;
-  if (!nc_shape(B, Cin, Cout, D, H, W, &sh, nullptr)) return 0;
+  const char* why;
+  if (!nc_shape(B, Cin, Cout, D, H, W, &sh, &why)) return 0;
   return align_up((size_t)sh.nrec * (size_t)Cout * ((size_t)Cin * NC_TAPS + 1) * sizeof(float)) + ALIGN;
 }
 
@@ -578,10 +562,7 @@ int mgs_narrow_conv3d_backward(int64_t B, int Cin, int Cout, int64_t D, int64_t 
   const char* fn = "narrow_conv3d_backward";
   NcShape sh;
   if (int rc = nc_check(fn, B, Cin, Cout, D, H, W, zeros_pad, &sh)) return rc;
-  if (split < 0 || split > NC_MAX_REC) {
-    set_error("%s: split = %d (0: chosen by the library, at most %d)", fn, split, NC_MAX_REC);
-    return MGS_ERR_INVALID_ARG;
-  }
+  if (int rc = split_check(fn, split)) return rc;
   if (!dx && !dw && !db) { set_error("%s: NULL dx, dw and db: no gradient is asked for", fn); return MGS_ERR_INVALID_ARG; }
   if (!g_y || (dx && !w) || (dw && !x)) { set_error("%s: NULL g_y, w (needed for dx) or x (needed for dw)", fn); return MGS_ERR_INVALID_ARG; }
   if (misaligned16(x) || misaligned16(g_y) || misaligned16(w) || misaligned16(dx) || misaligned16(dw) || misaligned16(db)) {
@@ -589,10 +570,8 @@ int mgs_narrow_conv3d_backward(int64_t B, int Cin, int Cout, int64_t D, int64_t 
     return MGS_ERR_INVALID_ARG;
   }
   const bool sums = dw || db;
-  if (sums) {
-    if (!workspace || misaligned16(workspace)) { set_error("%s: NULL or misaligned workspace", fn); return MGS_ERR_INVALID_ARG; }
-    if (int rc = workspace_short(fn, workspace_bytes, mgs_narrow_conv3d_workspace_bytes(B, Cin, Cout, D, H, W))) return rc;
-  }
+  if (sums)
+    if (int rc = records_workspace(fn, workspace, workspace_bytes, mgs_narrow_conv3d_workspace_bytes(B, Cin, Cout, D, H, W))) return rc;
   hipStream_t s = (hipStream_t)stream;
   const NcGeom g = nc_geom(sh, zeros_pad);
   if (dx) {
@@ -600,16 +579,14 @@ int mgs_narrow_conv3d_backward(int64_t B, int Cin, int Cout, int64_t D, int64_t 
     NC_LAUNCH(nc_bwd_data_kernel, Cout, grid, dim3(NC_GROUP), s, g, g_y, w, dx);
   }
   if (sums) {
-    int64_t wgs = split ? split : NC_MAX_REC;
-    wgs = wgs > sh.nrec ? sh.nrec : wgs;
+    const int64_t wgs = split_clamp(split, MAX_REC, sh.nrec);
     float* records = reinterpret_cast<float*>(workspace);
     const int want_dw = dw != nullptr;
     const int cig = Cout == 1 ? NcBw<1>::CIG : 1;
     const dim3 grid((unsigned)wgs, (unsigned)(want_dw ? (Cin + cig - 1) / cig : 1));
     NC_LAUNCH(nc_bwd_weight_kernel, Cout, grid, dim3(NC_GROUP), s, g, (uint32_t)sh.nrec, (uint32_t)sh.tpr, (uint32_t)sh.ntiles,
               want_dw, x, g_y, records);
-    const uint32_t cols = (uint32_t)(Cin * NC_TAPS + 1), total = (uint32_t)Cout * cols;
-    hipLaunchKernelGGL(nc_merge_kernel, dim3((total + 255u) / 256u), dim3(256), 0, s, (uint32_t)sh.nrec, cols, total, records, dw, db);
+    launch_records_merge(sh.nrec, Cout, Cin * NC_TAPS + 1, Cin * NC_TAPS, records, dw, db, s);
   }
   return launch_done(fn);
 }

@@ -19,7 +19,7 @@
 // No load sits behind a branch: a voxel or channel that is not there loads an element that is and drops it, so that all of a
 // thread's loads are in flight before the first is used.
 //
-// Backward, whenever dw or db is wanted (pw_bwd_kernel, pw_merge_kernel).  Tiles of TV = 64 VPL voxels (VPL = 4 voxels per lane up
+// Backward, whenever dw or db is wanted (pw_bwd_kernel; merge: mgs_records.hip).  Tiles of TV = 64 VPL voxels (VPL = 4 voxels per lane up
 // to 8 input channels, 2 up to 16), in their linear order over (batch, voxel), are cut into nrec <= 64 runs of tpr tiles; nrec and
 // tpr depend on the shape alone.  A workgroup of 8 waves takes a run.  Wave k owns output channels 8k .. 8k + 7 for the whole run:
 // per tile it reads ITS rows of g -- so every element of g is read from memory once, by one wave -- and the tile's x, and keeps
@@ -39,7 +39,6 @@
 namespace mgs {
 
 constexpr int PW_MAX_C = 64;
-constexpr int PW_MAX_REC = 64;              // most partial records of dw | db
 constexpr int PW_THREADS = 256;             // forward
 constexpr int PW_TILE = 4 * PW_THREADS;     // voxels per workgroup of the forward
 constexpr int PW_NARROW = 16;               // most input channels a thread of the forward keeps in registers
@@ -389,19 +388,6 @@ __global__ __launch_bounds__(PW_BWD_THREADS) void pw_bwd_kernel(PwBwd a) {
   }
 }
 
-// records [nrec, Cout, Cin + 1] -> dw [Cout, Cin], db [Cout] (either may be nullptr), in ascending order in double
-__global__ __launch_bounds__(PW_THREADS) void pw_merge_kernel(uint32_t nrec, int Cin, int Cout, const float* __restrict__ records,
-                                                              float* __restrict__ dw, float* __restrict__ db) {
-  const uint32_t e = blockIdx.x * PW_THREADS + threadIdx.x, cols = (uint32_t)Cin + 1u, total = (uint32_t)Cout * cols;
-  if (e >= total) return;
-  const uint32_t co = e / cols, c = e - co * cols;
-  if (c < (uint32_t)Cin ? dw == nullptr : db == nullptr) return;
-  double s = 0.0;
-  for (uint32_t r = 0; r < nrec; ++r) s += (double)records[(size_t)r * total + e];
-  if (c < (uint32_t)Cin) dw[co * (uint32_t)Cin + c] = (float)s;
-  else db[co] = (float)s;
-}
-
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 struct PwShape {
   int64_t B, n;
@@ -413,12 +399,10 @@ struct PwShape {
 };
 
 static bool pw_shape(int64_t B, int Cin, int Cout, int64_t n, PwShape* sh, const char** why) {
-  const char* unused;
-  if (!why) why = &unused;
   if (Cin < 1 || Cin > PW_MAX_C || Cout < 1 || Cout > PW_MAX_C) { *why = "channel counts must be 1 to 64"; return false; }
   if (B < 1 || n < 1) { *why = "B and n must be at least 1"; return false; }
+  if (row_too_long(1, 1, n)) { *why = "a (batch, channel) row must hold fewer than 2^31 elements"; return false; }
   const int64_t lim = 0x7fffffff;
-  if (n > lim) { *why = "a (batch, channel) row must hold fewer than 2^31 elements"; return false; }
   sh->B = B; sh->n = n; sh->Cin = Cin; sh->Cout = Cout;
   sh->vec = n % 4 == 0;
   sh->fwd_tiles_per_row = (n + PW_TILE - 1) / PW_TILE;
@@ -428,9 +412,8 @@ static bool pw_shape(int64_t B, int Cin, int Cout, int64_t n, PwShape* sh, const
   const int64_t finest = (n + 127) / 128;   // bounds the tile count of every launch from above
   if (B > lim / finest) { *why = "B times the number of tiles exceeds 2^31 - 1"; return false; }
   sh->ntiles = B * sh->tiles_per_row;
-  const int64_t want = sh->ntiles < PW_MAX_REC ? sh->ntiles : PW_MAX_REC;
-  sh->tpr = (sh->ntiles + want - 1) / want;
-  sh->nrec = (sh->ntiles + sh->tpr - 1) / sh->tpr;
+  const Runs runs = cut_runs(sh->ntiles, MAX_REC);
+  sh->nrec = runs.n; sh->tpr = runs.per;
   return true;
 }
 
@@ -482,7 +465,8 @@ extern "C" {
 
 size_t mgs_pointwise_workspace_bytes(int64_t B, int Cin, int Cout, int64_t n) {
   PwShape sh;
-  if (!pw_shape(B, Cin, Cout, n, &sh, nullptr)) return 0;
+  const char* why;
+  if (!pw_shape(B, Cin, Cout, n, &sh, &why)) return 0;
   return align_up((size_t)sh.nrec * (size_t)Cout * (size_t)(Cin + 1) * sizeof(float)) + ALIGN;
 }
 
@@ -505,10 +489,7 @@ int mgs_pointwise_backward(int64_t B, int Cin, int Cout, int64_t n, const float*
   const char* fn = "pointwise_backward";
   PwShape sh;
   if (int rc = pw_check(fn, B, Cin, Cout, n, &sh)) return rc;
-  if (split < 0 || split > PW_MAX_REC) {
-    set_error("%s: split = %d (0: chosen by the library, at most %d)", fn, split, PW_MAX_REC);
-    return MGS_ERR_INVALID_ARG;
-  }
+  if (int rc = split_check(fn, split)) return rc;
   if (!dx && !dw && !db) { set_error("%s: NULL dx, dw and db: no gradient is asked for", fn); return MGS_ERR_INVALID_ARG; }
   const bool sums = dw || db;
   if (!g_y || (dx && !w) || (sums && !x)) { set_error("%s: NULL g_y, w (needed for dx) or x (needed for dw and db)", fn); return MGS_ERR_INVALID_ARG; }
@@ -521,10 +502,8 @@ int mgs_pointwise_backward(int64_t B, int Cin, int Cout, int64_t n, const float*
     pw_launch_forward(sh, Cout, Cin, true, g_y, w, nullptr, dx, s);
     return launch_done(fn);
   }
-  if (!workspace || misaligned16(workspace)) { set_error("%s: NULL or misaligned workspace", fn); return MGS_ERR_INVALID_ARG; }
-  if (int rc = workspace_short(fn, workspace_bytes, mgs_pointwise_workspace_bytes(B, Cin, Cout, n))) return rc;
-  int64_t wgs = split ? split : PW_MAX_REC;
-  wgs = wgs > sh.nrec ? sh.nrec : wgs;
+  if (int rc = records_workspace(fn, workspace, workspace_bytes, mgs_pointwise_workspace_bytes(B, Cin, Cout, n))) return rc;
+  const int64_t wgs = split_clamp(split, MAX_REC, sh.nrec);
   PwBwd a;
   a.Cin = Cin; a.Cout = Cout; a.n = n;
   a.tiles_per_row = (uint32_t)sh.tiles_per_row; a.ntiles = (uint32_t)sh.ntiles;
@@ -544,9 +523,7 @@ int mgs_pointwise_backward(int64_t B, int Cin, int Cout, int64_t n, const float*
       else hipLaunchKernelGGL((pw_bwd_kernel<16, 2, false>), grid, block, 0, s, a);
     }
   }
-  const uint32_t total = (uint32_t)(Cout * (Cin + 1));
-  hipLaunchKernelGGL(pw_merge_kernel, dim3((total + PW_THREADS - 1) / PW_THREADS), dim3(PW_THREADS), 0, s, (uint32_t)sh.nrec, Cin, Cout,
-                     a.records, dw, db);
+  launch_records_merge(sh.nrec, Cout, Cin + 1, Cin, a.records, dw, db, s);
   return launch_done(fn);
 }
 

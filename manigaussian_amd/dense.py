@@ -18,8 +18,7 @@ import math
 
 import torch
 
-from . import _lib, _ops
-from .conv3d import _readable
+from . import _conv, _lib, _ops
 
 KERNELS = (3, 5)
 MIN_CIN, CIN_STEP, MIN_COUT, COUT_STEP, MAX_CHANNELS = 8, 8, 32, 32, 256
@@ -32,8 +31,8 @@ def _workspace(dev, B, cin, cout, k, ext):
 class _Dense(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, slope, split):
-        x, weight = _readable(x), _readable(weight)
-        bias = None if bias is None else _readable(bias)
+        x, weight = _ops.readable(x), _ops.readable(weight)
+        bias = None if bias is None else _ops.readable(bias)
         B, cin = x.shape[:2]
         cout, k = weight.size(0), weight.size(2)
         ext = tuple(x.shape[2:])
@@ -48,20 +47,16 @@ class _Dense(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, weight, y = ctx.saved_tensors
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        need_b = ctx.has_bias and ctx.needs_input_grad[2]
-        if not (need_x or need_w or need_b):
+        begun = _conv.backward_begin(ctx, x, weight, g)
+        if begun is None:
             return None, None, None, None, None
+        g, dx, dw, db = begun
         dev = x.device
         B, cin = x.shape[:2]
         cout, k = weight.size(0), weight.size(2)
         ext = tuple(x.shape[2:])
-        g = _readable(g)
-        dx = torch.empty_like(x) if need_x else None
-        dw = torch.empty_like(weight) if need_w else None
-        db = torch.empty(cout, dtype=torch.float32, device=dev) if need_b else None
         # the masked output gradient, zero-padded by k - 1 on every side: what the forward's kernel turns into dx
-        scratch = torch.empty((B, cout) + tuple(e + k - 1 for e in ext), dtype=torch.float32, device=dev) if need_x else None
+        scratch = torch.empty((B, cout) + tuple(e + k - 1 for e in ext), dtype=torch.float32, device=dev) if dx is not None else None
         ws = _workspace(dev, B, cin, cout, k, ext)   # the rearranged weights and the partial records, written before they are read
         _ops.call("mgs_dense_conv3d_backward", dev, B, cin, cout, k, *ext, ctx.slope, x.data_ptr(), y.data_ptr(), g.data_ptr(),
                   weight.data_ptr(), _ops.ptr(dx), _ops.ptr(dw), _ops.ptr(db), _ops.ptr(scratch), ws.data_ptr(), ws.numel(), ctx.split)
@@ -77,26 +72,15 @@ def eligible(cin, cout, kernel, ext):
 def _dense_conv3d(x, weight, bias=None, negative_slope=None, split=0):
     """dense_conv3d with `split`: 0 = the library's split of the partial sums of dw and db over workgroups, 1..64 = that many (a
     test aid)."""
-    for name, t in (("x", x), ("weight", weight), ("bias", bias)):
-        if t is None and name == "bias":
-            continue
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-            raise RuntimeError(f"dense_conv3d needs float32 tensors on a HIP device ({name} is "
-                               f"{getattr(t, 'dtype', type(t))} on {getattr(t, 'device', 'the host')}); there is no CPU path")
+    _ops.need_float32("dense_conv3d", ("bias",), x=x, weight=weight, bias=bias)
     if negative_slope is not None and not (isinstance(negative_slope, (int, float)) and negative_slope >= 0):
         raise ValueError(f"negative_slope = {negative_slope!r}: None (no activation) or a number >= 0")
-    if x.dim() != 5 or x.numel() == 0:
-        raise ValueError(f"expected x [B,C,D,H,W] with no empty dimension, got {tuple(x.shape)}")
-    if weight.dim() != 5 or weight.size(2) not in KERNELS or len(set(weight.shape[2:])) != 1 or weight.size(1) != x.size(1):
-        raise ValueError(f"weight {tuple(weight.shape)} is not a 3x3x3 or 5x5x5 kernel over the {x.size(1)} channels of x")
-    if weight.device != x.device:
-        raise ValueError(f"weight must be on {x.device}")
+    _conv.check_shapes(x, weight, KERNELS)
     cout, cin, k = weight.shape[:3]
     if not (MIN_CIN <= cin <= MAX_CHANNELS and cin % CIN_STEP == 0 and MIN_COUT <= cout <= MAX_CHANNELS and cout % COUT_STEP == 0):
         raise ValueError(f"weight {tuple(weight.shape)}: a multiple of {COUT_STEP} in {MIN_COUT}..{MAX_CHANNELS} output and a multiple of "
                          f"{CIN_STEP} in {MIN_CIN}..{MAX_CHANNELS} input channels")
-    if bias is not None and (tuple(bias.shape) != (cout,) or bias.device != x.device):
-        raise ValueError(f"bias must be a [{cout}] tensor on {x.device}, got {tuple(bias.shape)} on {bias.device}")
+    _conv.check_bias(x, weight, bias)
     if min(x.shape[2:]) < k:
         raise ValueError(f"x {tuple(x.shape)}: every extent must be at least the kernel's {k}")
     if math.prod(e + k - 1 for e in x.shape[2:]) >= 2 ** 31:

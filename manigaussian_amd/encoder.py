@@ -21,8 +21,8 @@ eval mode with gradients enabled -- and wherever fused_site() says the fused op 
 import torch
 from torch import nn
 
-from . import _lib, _ops
-from .conv3d import _readable, conv3d, conv_transpose3d
+from . import _conv, _lib, _ops
+from .conv3d import conv3d, conv_transpose3d
 from .pointwise import pointwise_conv3d
 
 MAX_C = 65536
@@ -74,10 +74,8 @@ def conv_site(cin, cout, voxels, stride, transposed):
 
 def _conv_routed(conv, x, transposed):
     """Whether `conv` (a bias-free 3x3x3 nn.Conv3d / stride-2 nn.ConvTranspose3d of the stem's kind) on x goes through the kernels."""
-    if CONV is False or FORCE is False or not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
-        return False
     w = conv.weight
-    if x.dim() != 5 or x.numel() == 0 or conv.bias is not None or w.dtype != torch.float32 or w.device != x.device:
+    if CONV is False or FORCE is False or conv.bias is not None or not _conv.routable(x, w):
         return False
     if conv.kernel_size != (3, 3, 3) or conv.padding != (1, 1, 1) or conv.dilation != (1, 1, 1) or conv.groups != 1:
         return False
@@ -123,12 +121,8 @@ def pointwise_site(cin, cout, values_per_channel):
 
 def _pointwise_routed(conv, x):
     """Whether `conv` (a 1x1x1 nn.Conv3d of conv_out's kind, with or without a bias) on x goes through the kernels."""
-    if POINTWISE is False or FORCE is False or not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
-        return False
-    w, b = conv.weight, conv.bias
-    if x.dim() != 5 or x.numel() == 0 or w.dtype != torch.float32 or w.device != x.device:
-        return False
-    if b is not None and (b.dtype != torch.float32 or b.device != x.device):
+    w = conv.weight
+    if POINTWISE is False or FORCE is False or not _conv.routable(x, w, conv.bias):
         return False
     if conv.kernel_size != (1, 1, 1) or conv.stride != (1, 1, 1) or conv.padding != (0, 0, 0) or conv.dilation != (1, 1, 1):
         return False
@@ -143,8 +137,8 @@ class _BatchNormAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, residual, running_mean, running_var, num_batches_tracked, training, momentum, eps, slope,
                 slices):
-        x = _readable(x)
-        res = None if residual is None else _readable(residual)
+        x = _ops.readable(x)
+        res = None if residual is None else _ops.readable(residual)
         dev = x.device
         B, C = x.shape[:2]
         n = x[0, 0].numel()
@@ -171,7 +165,7 @@ class _BatchNormAct(torch.autograd.Function):
         dev = x.device
         B, C = x.shape[:2]
         n = x[0, 0].numel()
-        gy = _readable(g)
+        gy = _ops.readable(g)
         dx = torch.empty_like(x)
         dwb = torch.empty(2, C, dtype=torch.float32, device=dev)
         ws = _ops.workspace(dev, _lib.lib().mgs_abn_workspace_bytes(B, C, n))
@@ -186,12 +180,7 @@ class _BatchNormAct(torch.autograd.Function):
 def _batch_norm_act(x, weight, bias, running_mean, running_var, num_batches_tracked, training, momentum, eps, negative_slope,
                     residual, slices=0):
     """batch_norm_act with `slices`: 0 = the library's split of a row over workgroups, 1..64 = that many (a test aid)."""
-    for name, t in (("x", x), ("residual", residual)):
-        if t is None and name == "residual":
-            continue
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-            raise RuntimeError(f"batch_norm_act needs float32 tensors on a HIP device ({name} is "
-                               f"{getattr(t, 'dtype', type(t))} on {getattr(t, 'device', 'the host')}); there is no CPU path")
+    _ops.need_float32("batch_norm_act", ("residual",), x=x, residual=residual)
     if x.dim() != 5 or x.numel() == 0:
         raise ValueError(f"expected x [B,C,D,H,W] with no empty dimension, got {tuple(x.shape)}")
     if residual is not None and residual.shape != x.shape:

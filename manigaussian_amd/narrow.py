@@ -13,8 +13,7 @@ allocation beyond the outputs and the device's shared workspace: capturable into
 """
 import torch
 
-from . import _lib, _ops
-from .conv3d import _readable
+from . import _conv, _lib, _ops
 
 MAX_CIN, MAX_COUT = 256, 4
 PADDING_MODES = ("replicate", "zeros")
@@ -23,8 +22,8 @@ PADDING_MODES = ("replicate", "zeros")
 class _Narrow(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, zeros, split):
-        x, weight = _readable(x), _readable(weight)
-        bias = None if bias is None else _readable(bias)
+        x, weight = _ops.readable(x), _ops.readable(weight)
+        bias = None if bias is None else _ops.readable(bias)
         B, cin = x.shape[:2]
         cout = weight.size(0)
         ext = tuple(x.shape[2:])
@@ -38,20 +37,16 @@ class _Narrow(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, weight = ctx.saved_tensors
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        need_b = ctx.has_bias and ctx.needs_input_grad[2]
-        if not (need_x or need_w or need_b):
+        begun = _conv.backward_begin(ctx, x, weight, g)
+        if begun is None:
             return None, None, None, None, None
+        g, dx, dw, db = begun
         dev = x.device
         B, cin = x.shape[:2]
         cout = weight.size(0)
         ext = tuple(x.shape[2:])
-        g = _readable(g)
-        dx = torch.empty_like(x) if need_x else None
-        dw = torch.empty_like(weight) if need_w else None
-        db = torch.empty(cout, dtype=torch.float32, device=dev) if need_b else None
         ws = None
-        if need_w or need_b:
+        if dw is not None or db is not None:
             # the partial records: written by the first launch before the second reads them
             ws = _ops.workspace(dev, _lib.lib().mgs_narrow_conv3d_workspace_bytes(B, cin, cout, *ext))
         _ops.call("mgs_narrow_conv3d_backward", dev, B, cin, cout, *ext, ctx.zeros, x.data_ptr(), g.data_ptr(), weight.data_ptr(),
@@ -62,26 +57,14 @@ class _Narrow(torch.autograd.Function):
 def _narrow_conv3d(x, weight, bias=None, padding_mode="replicate", split=0):
     """narrow_conv3d with `split`: 0 = the library's split of the partial sums of dw and db over workgroups, 1..64 = that many (a
     test aid)."""
-    for name, t in (("x", x), ("weight", weight), ("bias", bias)):
-        if t is None and name == "bias":
-            continue
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-            raise RuntimeError(f"narrow_conv3d needs float32 tensors on a HIP device ({name} is "
-                               f"{getattr(t, 'dtype', type(t))} on {getattr(t, 'device', 'the host')}); there is no CPU path")
+    _ops.need_float32("narrow_conv3d", ("bias",), x=x, weight=weight, bias=bias)
     if padding_mode not in PADDING_MODES:
         raise ValueError(f"padding_mode = {padding_mode!r}: 'replicate' or 'zeros'")
-    if x.dim() != 5 or x.numel() == 0:
-        raise ValueError(f"expected x [B,C,D,H,W] with no empty dimension, got {tuple(x.shape)}")
-    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or weight.size(1) != x.size(1):
-        raise ValueError(f"weight {tuple(weight.shape)} is not a 3x3x3 kernel over the {x.size(1)} channels of x")
-    if weight.device != x.device:
-        raise ValueError(f"weight must be on {x.device}")
+    _conv.check_shapes(x, weight, (3,))
     if not (1 <= weight.size(0) <= MAX_COUT and 1 <= weight.size(1) <= MAX_CIN):
         raise ValueError(f"weight {tuple(weight.shape)}: 1 to {MAX_COUT} output and 1 to {MAX_CIN} input channels")
-    if bias is not None and (tuple(bias.shape) != (weight.size(0),) or bias.device != x.device):
-        raise ValueError(f"bias must be a [{weight.size(0)}] tensor on {x.device}, got {tuple(bias.shape)} on {bias.device}")
-    if x[0, 0].numel() >= 2 ** 31:
-        raise ValueError(f"x {tuple(x.shape)}: a (batch, channel) row must hold fewer than 2^31 elements")
+    _conv.check_bias(x, weight, bias)
+    _conv.check_rows(x)
     return _Narrow.apply(x, weight, bias, int(padding_mode == "zeros"), int(split))
 
 

@@ -21,12 +21,6 @@ from . import _lib, _ops
 
 STATS = 6  # floats per (batch, channel): max, sum, E_x, E_y, E_z, argmax (the bits of a uint32)
 
-def _readable(t):
-    """The tensor itself when the kernels can read it in place (contiguous, 16-byte aligned), else one contiguous copy."""
-    if t.is_contiguous() and t.data_ptr() % 16 == 0:
-        return t
-    return t.contiguous() if not t.is_contiguous() else t.clone()
-
 
 def _rows_by_stride(t):
     """A [B, n] upstream gradient the kernels read by row stride."""
@@ -38,7 +32,7 @@ class _SpatialSoftmax3D(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feature, temperature, slices):
-        feature = _readable(feature)
+        feature = _ops.readable(feature)
         dev = feature.device
         B, C, D, H, W = feature.shape
         rows, n = B * C, D * H * W

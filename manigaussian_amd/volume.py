@@ -24,7 +24,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _lib, _ops
+from . import _conv, _lib, _ops
 from . import dense as _dense
 from .dense import dense_conv3d
 from .narrow import MAX_CIN as NARROW_MAX_CIN, MAX_COUT as NARROW_MAX_COUT, narrow_conv3d
@@ -52,12 +52,7 @@ def narrow_site(cin, cout, voxels):
 
 def _narrow_routed(conv, x):
     """Whether `conv` (a 3x3x3 nn.Conv3d of trans_decoder's kind) on x goes through the kernels."""
-    if NARROW is False or not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
-        return False
-    w, b = conv.weight, conv.bias
-    if x.dim() != 5 or x.numel() == 0 or w.dtype != torch.float32 or w.device != x.device:
-        return False
-    if b is not None and (b.dtype != torch.float32 or b.device != x.device):
+    if NARROW is False or not _conv.routable(x, conv.weight, conv.bias):
         return False
     if conv.kernel_size != (3, 3, 3) or conv.stride != (1, 1, 1) or conv.padding != (1, 1, 1) or conv.dilation != (1, 1, 1):
         return False
@@ -99,12 +94,7 @@ def _dense_slope(activation):
 
 def _dense_routed(conv, x):
     """Whether `conv` on x, the volume that already carries its padding, goes through the kernels."""
-    if DENSE is False or not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
-        return False
-    w, b = conv.weight, conv.bias
-    if x.dim() != 5 or x.numel() == 0 or w.dtype != torch.float32 or w.device != x.device:
-        return False
-    if b is not None and (b.dtype != torch.float32 or b.device != x.device):
+    if DENSE is False or not _conv.routable(x, conv.weight, conv.bias):
         return False
     k = conv.kernel_size
     if len(set(k)) != 1 or conv.stride != (1, 1, 1) or conv.dilation != (1, 1, 1) or conv.groups != 1 or x.size(1) != conv.in_channels:

@@ -6,7 +6,7 @@ import ctypes
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+gpu = pytest.mark.gpu
 
 
 def _ops_lib():
@@ -25,6 +25,7 @@ def _volume(shape, dev):
 
 
 # ---- stream ------------------------------------------------------------------------------------------------------------------
+@gpu
 def test_stream_is_the_current_stream_of_the_device():
     _ops, _ = _ops_lib()
     dev = torch.device("cuda:0")
@@ -37,6 +38,7 @@ def test_stream_is_the_current_stream_of_the_device():
     assert _raw(dev) == torch.cuda.current_stream(dev).cuda_stream
 
 
+@gpu
 def test_an_op_enqueued_under_a_stream_runs_on_it():
     from manigaussian_amd.spatial_softmax import spatial_softmax3d
     dev = torch.device("cuda:0")
@@ -53,6 +55,7 @@ def test_an_op_enqueued_under_a_stream_runs_on_it():
 
 
 # ---- workspace ---------------------------------------------------------------------------------------------------------------
+@gpu
 def test_workspace_is_one_tensor_per_device_and_size():
     _ops, _ = _ops_lib()
     dev = torch.device("cuda:0")
@@ -66,7 +69,27 @@ def test_workspace_is_one_tensor_per_device_and_size():
         assert _ops.workspace(torch.device("cuda"), 4096) is a  # no index: the current device's entry
 
 
+# ---- a tensor the kernels can read in place (no GPU needed) ------------------------------------------------------------------
+def test_readable_keeps_a_contiguous_aligned_tensor_and_copies_the_rest():
+    _ops, _ = _ops_lib()
+    t = torch.arange(24.0).view(2, 3, 4)
+    assert t.is_contiguous() and t.data_ptr() % 16 == 0
+    assert _ops.readable(t) is t
+    v = t.transpose(0, 2)
+    assert not v.is_contiguous()
+    c = _ops.readable(v)
+    assert c is not v and c.is_contiguous() and c.data_ptr() % 16 == 0 and c.shape == v.shape and torch.equal(c, v)
+    base = torch.zeros(9)
+    assert base.data_ptr() % 16 == 0
+    o = base[1:]
+    o += torch.arange(8.0)
+    assert o.is_contiguous() and o.data_ptr() % 16 == 4
+    a = _ops.readable(o)
+    assert a is not o and a.data_ptr() != o.data_ptr() and a.is_contiguous() and a.data_ptr() % 16 == 0 and torch.equal(a, o)
+
+
 # ---- the checked call --------------------------------------------------------------------------------------------------------
+@gpu
 def test_call_raises_the_library_s_message_under_the_symbol_s_name():
     _ops, _ = _ops_lib()
     dev = torch.device("cuda:0")
@@ -75,6 +98,7 @@ def test_call_raises_the_library_s_message_under_the_symbol_s_name():
         _ops.call("mgs_spatial_softmax_forward", dev, 0, 1, 1, 1, 1, 0.01, None, None, 0, None, 0, None, None, 0, 0)
 
 
+@gpu
 def test_call_looks_the_symbol_up_at_call_time(monkeypatch):
     _ops, _lib = _ops_lib()
     dev = torch.device("cuda:0")
@@ -91,6 +115,7 @@ def test_call_looks_the_symbol_up_at_call_time(monkeypatch):
 
 
 # ---- a device that is not current --------------------------------------------------------------------------------------------
+@gpu
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two devices")
 def test_an_op_on_another_device_runs_there_and_leaves_the_current_device():
     from manigaussian_amd.spatial_softmax import spatial_softmax3d

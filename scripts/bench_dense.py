@@ -45,7 +45,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
-from bench_conv3d import RUNS, SAMPLE_MS, Timer, benchmark_on  # noqa: E402
+from bench_conv3d import RUNS, SAMPLE_MS, Timer, benchmark_on, op_wins  # noqa: E402
 
 SLOPE = 0.02
 # name: cin, cout, k, unpadded side; in the order they run (a site's smaller size first)
@@ -255,18 +255,6 @@ def child(args):
     return 0
 
 
-def op_wins(entry):
-    """bench_conv3d.op_wins, with a torch_benchmark side that may not have finished."""
-    for p in ("forward", "forward_backward"):
-        for f in ("eager", "graph"):
-            sides = entry[p][f]
-            ts = [sides[s] for s in ("torch", "torch_benchmark") if s in sides and "median_us" in sides[s]]
-            t = min(ts, key=lambda s: s["median_us"])
-            if not sides["op"]["q3_us"] < t["q1_us"]:
-                return False
-    return True
-
-
 def routing(result):
     from manigaussian_amd import volume as vol
     result["routing_in_the_package"] = {k: bool(vol.dense_site(v["cin"], v["cout"], v["k"], v["voxels"])) for k, v in result["shapes"].items()}
@@ -383,7 +371,7 @@ def main():
             for p in ("forward", "forward_backward"):
                 for f in ("eager", "graph"):
                     entry[p][f]["torch_benchmark"] = note
-        entry["op_wins"] = op_wins(entry)
+        entry["op_wins"] = op_wins(entry, benchmark_may_be_missing=True)   # (a torch_benchmark child may not have finished)
 
     result["routing_as_measured"] = {k: v["op_wins"] for k, v in result["shapes"].items()}
     routing(result)

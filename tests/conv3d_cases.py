@@ -1,10 +1,6 @@
-"""Cases, inputs, references and the bound shared by tests/test_conv3d.py and tests/tools/conv3d_graph_capture_check.py -- TEST
-INFRASTRUCTURE.
-
-The reference is torch's own F.conv3d / F.conv_transpose3d on the CPU, computed at test time, once per case and shared (do not modify
-what reference() returns): in float64 -- the truth -- and in float32 -- the yardstick: its largest deviation from the truth over the
-truth's largest magnitude.  The bound is abn_cases': error <= 16 x max(yardstick, 2^-23) x max|truth|; a case whose yardstick exceeds
-abn_cases.REF_ERR_CEILING is refused, not loosened.
+"""The direct family's cases and inputs for tests/test_conv3d.py and tests/tools/conv_graph_capture_check.py -- TEST INFRASTRUCTURE.
+The reference is torch's own F.conv3d / F.conv_transpose3d on the CPU; how it is shared, its yardstick and the bound:
+tests/conv_cases.py.
 
 The kernels' own tiles (csrc/mgs_conv3d.hip), which the seam cases straddle:
   forward / backward-weight, and backward-data at stride 1: an OUTPUT tile of 4 x 8 x 32 (D x H x W) at stride 1, 2 x 8 x 32 at stride 2;
@@ -17,7 +13,8 @@ The kernels' own tiles (csrc/mgs_conv3d.hip), which the seam cases straddle:
 import torch
 import torch.nn.functional as F
 
-from abn_cases import FACTOR, FLOOR, REF_ERR_CEILING, bound, same_bits  # noqa: F401
+import conv_cases
+from conv_cases import FACTOR, FLOOR, REF_ERR_CEILING, bound, same_bits  # noqa: F401
 
 TILE_S1 = (4, 8, 32)
 TILE_S2 = (2, 8, 32)
@@ -54,6 +51,10 @@ def is_transposed(case):
     return case in TRANSPOSED
 
 
+def quantities(case):
+    return QUANTITIES   # (no bias)
+
+
 def make_inputs(case):
     """{x, w, g}: fp32 CPU tensors from a seeded generator; weights scaled by (27 Cin)^-1/2."""
     c = TRANSPOSED[case] if is_transposed(case) else CASES[case]
@@ -83,18 +84,6 @@ def torchs(case, t, dtype, device="cpu"):
     return {"y": y.detach(), "dx": x.grad, "dw": w.grad}
 
 
-_REFERENCES = {}
-
-
 def reference(case):
     """{x, w, g (float32), y64, dx64, dw64, ref_err: {quantity: yardstick}}, computed once and shared."""
-    if case not in _REFERENCES:
-        t = make_inputs(case)
-        r64, r32 = torchs(case, t, torch.float64), torchs(case, t, torch.float32)
-        r = dict(t)
-        r["ref_err"] = {}
-        for q in QUANTITIES:
-            r[q + "64"] = r64[q]
-            r["ref_err"][q] = (r32[q].double() - r64[q]).abs().max().item() / r64[q].abs().max().item()
-        _REFERENCES[case] = r
-    return _REFERENCES[case]
+    return conv_cases.reference("conv3d", case, lambda: make_inputs(case), lambda t, dtype: torchs(case, t, dtype), QUANTITIES)

@@ -1,10 +1,6 @@
-"""Cases, inputs, references and the bound shared by tests/test_dense_conv.py and tests/tools/dense_graph_capture_check.py -- TEST
-INFRASTRUCTURE.
-
-The reference is torch's own F.conv3d (+ F.leaky_relu) on the CPU, computed at test time, once per case and shared (do not modify
-what reference() returns): in float64 -- the truth -- and in float32 -- the yardstick: its largest deviation from the truth over the
-truth's largest magnitude.  The bound is abn_cases': error <= 16 x max(yardstick, 2^-23) x max|truth|; a case whose yardstick exceeds
-abn_cases.REF_ERR_CEILING is refused, not loosened.
+"""The dense family's cases and inputs for tests/test_dense_conv.py and tests/tools/conv_graph_capture_check.py -- TEST
+INFRASTRUCTURE.  The reference is torch's own F.conv3d (+ F.leaky_relu) on the CPU; how it is shared, its yardstick and the bound:
+tests/conv_cases.py.
 
 A case with an activation walks the generator's seeds from its fixed base until no pre-activation has |z64| < abn_cases.KINK (with and
 without the bias: the cases that share its data drop it): a float32 run could otherwise legitimately take the other branch.  The two
@@ -19,7 +15,9 @@ cuts the segments into at most MAX_RUNS records.
 import torch
 import torch.nn.functional as F
 
-from abn_cases import FACTOR, FLOOR, KINK, REF_ERR_CEILING, bound, same_bits  # noqa: F401
+import conv_cases
+from abn_cases import KINK
+from conv_cases import FACTOR, FLOOR, REF_ERR_CEILING, bound, same_bits  # noqa: F401
 
 M_TILE, N_TILE, K_SLAB = 128, 128, 8
 W_SEG, W_NTILE = 64, 128
@@ -63,7 +61,7 @@ def slope_of(case):
 
 
 def quantities(case):
-    return ("y", "dx", "dw", "db") if has_bias(case) else ("y", "dx", "dw")
+    return conv_cases.quantities(has_bias(case))
 
 
 def in_extents(ext, k):
@@ -138,23 +136,11 @@ def torchs(t, dtype, slope, device="cpu", with_z=False):
     return r
 
 
-_REFERENCES = {}
-
-
 def reference(case):
     """{x, w, b, g (float32), z64, y64, dx64, dw64, db64, ref_err: {quantity: yardstick}}, computed once and shared."""
-    if case not in _REFERENCES:
-        t = exact_inputs(case) if case in EXACT else make_inputs(case)
-        slope = slope_of(case)
-        r64, r32 = torchs(t, torch.float64, slope, with_z=True), torchs(t, torch.float32, slope)
-        r = dict(t)
-        r["z64"] = r64["z"]
-        r["ref_err"] = {}
-        for q in quantities(case):
-            r[q + "64"] = r64[q]
-            r["ref_err"][q] = (r32[q].double() - r64[q]).abs().max().item() / r64[q].abs().max().item()
-        _REFERENCES[case] = r
-    return _REFERENCES[case]
+    return conv_cases.reference("dense", case, lambda: exact_inputs(case) if case in EXACT else make_inputs(case),
+                                lambda t, dtype: torchs(t, dtype, slope_of(case), with_z=dtype is torch.float64), quantities(case),
+                                also=("z",))
 
 
 def exact_partial_sum_bound(case):

@@ -1,10 +1,6 @@
-"""Cases, inputs, references and the bound shared by tests/test_narrow_conv.py and tests/tools/narrow_graph_capture_check.py -- TEST
-INFRASTRUCTURE.
-
-The reference is torch's own F.conv3d(F.pad(x, (1,) * 6, mode), w, b) on the CPU, computed at test time, once per case and shared (do
-not modify what reference() returns): in float64 -- the truth -- and in float32 -- the yardstick: its largest deviation from the
-truth over the truth's largest magnitude.  The bound is abn_cases': error <= 16 x max(yardstick, 2^-23) x max|truth|; a case whose
-yardstick exceeds abn_cases.REF_ERR_CEILING is refused, not loosened.
+"""The narrow-output family's cases and inputs for tests/test_narrow_conv.py and tests/tools/conv_graph_capture_check.py -- TEST
+INFRASTRUCTURE.  The reference is torch's own F.conv3d(F.pad(x, (1,) * 6, mode), w, b) on the CPU; how it is shared, its yardstick and
+the bound: tests/conv_cases.py.
 
 The kernels' own tile (csrc/mgs_narrow.hip), which the seam cases straddle: TILE_W x TILE_H x TILE_D = 32 x 8 x 8 voxels per group of
 128 threads, a register block of 4 (D) x 4 (W) voxels per thread; rows whose length is a multiple of 4 are stored 16 bytes at a time,
@@ -14,7 +10,8 @@ weight gradient 2 (Cout = 1) or 1; the partial records: at most 64 runs of tiles
 import torch
 import torch.nn.functional as F
 
-from abn_cases import FACTOR, FLOOR, REF_ERR_CEILING, bound, same_bits  # noqa: F401
+import conv_cases
+from conv_cases import FACTOR, FLOOR, REF_ERR_CEILING, bound, same_bits  # noqa: F401
 
 TILE_W, TILE_H, TILE_D = 32, 8, 8
 MAX_RUNS = 64
@@ -41,15 +38,15 @@ ALL = list(CASES)
 
 
 def has_bias(case):
-    return CASES[case]["shape"][4]
+    return case == "exact" or conv_cases.has_bias(CASES, case)
 
 
 def mode_of(case):
-    return CASES[case]["mode"]
+    return "replicate" if case == "exact" else CASES[case]["mode"]
 
 
 def quantities(case):
-    return ("y", "dx", "dw", "db") if has_bias(case) else ("y", "dx", "dw")
+    return conv_cases.quantities(has_bias(case))
 
 
 def make_inputs(case):
@@ -83,20 +80,7 @@ def torchs(t, dtype, mode="replicate", device="cpu"):
     return {"y": y.detach(), "dx": x.grad, "dw": w.grad, "db": None if b is None else b.grad}
 
 
-_REFERENCES = {}
-
-
 def reference(case):
     """{x, w, b, g (float32), y64, dx64, dw64, db64, ref_err: {quantity: yardstick}}, computed once and shared."""
-    if case not in _REFERENCES:
-        exact = case == "exact"
-        t = exact_inputs() if exact else make_inputs(case)
-        mode = "replicate" if exact else mode_of(case)
-        r64, r32 = torchs(t, torch.float64, mode), torchs(t, torch.float32, mode)
-        r = dict(t)
-        r["ref_err"] = {}
-        for q in ("y", "dx", "dw", "db") if exact else quantities(case):
-            r[q + "64"] = r64[q]
-            r["ref_err"][q] = (r32[q].double() - r64[q]).abs().max().item() / r64[q].abs().max().item()
-        _REFERENCES[case] = r
-    return _REFERENCES[case]
+    return conv_cases.reference("narrow", case, exact_inputs if case == "exact" else lambda: make_inputs(case),
+                                lambda t, dtype: torchs(t, dtype, mode_of(case)), quantities(case))

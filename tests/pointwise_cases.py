@@ -1,10 +1,5 @@
-"""Cases, inputs, references and the bound shared by tests/test_pointwise.py and tests/tools/pointwise_graph_capture_check.py -- TEST
-INFRASTRUCTURE.
-
-The reference is torch's own F.conv3d on the CPU, computed at test time, once per case and shared (do not modify what reference()
-returns): in float64 -- the truth -- and in float32 -- the yardstick: its largest deviation from the truth over the truth's largest
-magnitude.  The bound is abn_cases': error <= 16 x max(yardstick, 2^-23) x max|truth|; a case whose yardstick exceeds
-abn_cases.REF_ERR_CEILING is refused, not loosened.
+"""The pointwise family's cases and inputs for tests/test_pointwise.py and tests/tools/conv_graph_capture_check.py -- TEST
+INFRASTRUCTURE.  The reference is torch's own F.conv3d on the CPU; how it is shared, its yardstick and the bound: tests/conv_cases.py.
 
 The kernels' own tiles (csrc/mgs_pointwise.hip), which the seam cases straddle; n = D H W:
   forward (and the input gradient alone): 1024 consecutive voxels per workgroup, 4 per thread; 16-byte accesses where n is a multiple
@@ -15,7 +10,8 @@ The kernels' own tiles (csrc/mgs_pointwise.hip), which the seam cases straddle; 
 import torch
 import torch.nn.functional as F
 
-from abn_cases import FACTOR, FLOOR, REF_ERR_CEILING, bound, same_bits  # noqa: F401
+import conv_cases
+from conv_cases import FACTOR, FLOOR, REF_ERR_CEILING, bound, same_bits  # noqa: F401
 
 FWD_TILE = 1024
 BWD_TILE_8, BWD_TILE_16 = 256, 128
@@ -45,11 +41,11 @@ ALL = list(CASES)
 
 
 def has_bias(case):
-    return CASES[case]["shape"][4]
+    return conv_cases.has_bias(CASES, case)
 
 
 def quantities(case):
-    return ("y", "dx", "dw", "db") if has_bias(case) else ("y", "dx", "dw")
+    return conv_cases.quantities(has_bias(case))
 
 
 def make_inputs(case):
@@ -74,18 +70,6 @@ def torchs(t, dtype, device="cpu"):
     return {"y": y.detach(), "dx": x.grad, "dw": w.grad, "db": None if b is None else b.grad}
 
 
-_REFERENCES = {}
-
-
 def reference(case):
     """{x, w, b, g (float32), y64, dx64, dw64, db64, ref_err: {quantity: yardstick}}, computed once and shared."""
-    if case not in _REFERENCES:
-        t = make_inputs(case)
-        r64, r32 = torchs(t, torch.float64), torchs(t, torch.float32)
-        r = dict(t)
-        r["ref_err"] = {}
-        for q in quantities(case):
-            r[q + "64"] = r64[q]
-            r["ref_err"][q] = (r32[q].double() - r64[q]).abs().max().item() / r64[q].abs().max().item()
-        _REFERENCES[case] = r
-    return _REFERENCES[case]
+    return conv_cases.reference("pointwise", case, lambda: make_inputs(case), torchs, quantities(case))

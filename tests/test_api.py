@@ -3,11 +3,11 @@ declares, the Python surface matches the reference's (field order, signatures, e
 product path refuses to run without a HIP device instead of falling back."""
 import inspect
 import os
-import re
 
 import pytest
 import torch
 
+import conv_family
 from manigaussian_amd import _C, _lib
 import diff_gaussian_rasterization as dgr
 
@@ -15,13 +15,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_library_exports_every_declared_symbol():
-    hdr = open(os.path.join(ROOT, "include", "mgsplat.h")).read()
-    declared = set(re.findall(r"\b(mgs_[a-z0-9_]+)\s*\(", hdr)) - {"mgs_stream_t"}
-    assert declared, "no declarations parsed"
     L = _lib.lib()  # binds every symbol in _lib._EXPORTS; raises if one is missing
-    for name in declared:
-        assert hasattr(L, name), f"{name} declared in mgsplat.h but not exported by libmgsplat.so"
-    assert set(_lib.exported_symbols()) == declared, "ctypes table and header disagree"
+    conv_family.check_abi()   # the names, and every entry point's argument count and size type, against include/mgsplat.h
     assert L.mgs_abi_version() == _lib.ABI_VERSION
 
 

@@ -2,25 +2,24 @@
 torch's own F.conv3d / F.conv_transpose3d on the CPU (tests/conv3d_cases.py): float64 is the truth, the float32 CPU run the yardstick,
     |ours - truth| <= 16 x max(yardstick, 2^-23) x max|truth|    for y, dx and dw of every case.
 """
-import ctypes
 import importlib
 import json
 import os
 import re
-import subprocess
-import sys
 
 import pytest
 import torch
 
 import conv3d_cases as cc
+import conv_family as cf
 from manigaussian_amd import _lib
 from manigaussian_amd import encoder as enc
 
 cv = importlib.import_module("manigaussian_amd.conv3d")   # (the package's attribute of that name is the function)
 
 gpu = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = cf.ROOT
+FAMILY = cf.FAMILIES["conv3d"]
 STEM_SITES = ["conv0", "conv1", "conv2", "conv3", "conv4", "conv5", "conv6", "conv7", "conv9", "conv11"]
 
 
@@ -36,28 +35,13 @@ def route():
 
 
 # ---- CPU ---------------------------------------------------------------------------------------------------------------------
-FAKE = 0x10000
-
-
-def _args(kw, names):
-    a = dict(B=1, Cin=4, Cout=8, D=5, H=6, W=7, stride=1, x=FAKE, w=FAKE, y=FAKE, g=FAKE, dx=FAKE, dw=FAKE, ws=FAKE, ws_bytes=None,
-             split=0)
-    a.update(kw)
-    if a["ws_bytes"] is None:
-        a["ws_bytes"] = max(_lib.lib().mgs_conv3d_workspace_bytes(*(a[k] for k in ("B", "Cin", "Cout", "D", "H", "W", "stride"))), 256)
-    return [a[k] for k in ("B", "Cin", "Cout", "D", "H", "W", "stride") + names] + [None]
-
-
-def _fwd(**kw):
-    return _lib.lib().mgs_conv3d_forward(*_args(kw, ("x", "w", "y")))
-
-
-def _bwd_data(**kw):
-    return _lib.lib().mgs_conv3d_backward_data(*_args(kw, ("g", "w", "dx")))
-
-
-def _bwd_weight(**kw):
-    return _lib.lib().mgs_conv3d_backward_weight(*_args(kw, ("x", "g", "dw", "ws", "ws_bytes", "split")))
+FAKE = cf.FAKE
+SHAPE = ("B", "Cin", "Cout", "D", "H", "W", "stride")
+DEFAULTS = dict(B=1, Cin=4, Cout=8, D=5, H=6, W=7, stride=1, x=FAKE, w=FAKE, y=FAKE, g=FAKE, dx=FAKE, dw=FAKE, ws=FAKE)
+_fwd = cf.fake_args("mgs_conv3d_forward", "mgs_conv3d_workspace_bytes", SHAPE, DEFAULTS, ("x", "w", "y"))
+_bwd_data = cf.fake_args("mgs_conv3d_backward_data", "mgs_conv3d_workspace_bytes", SHAPE, DEFAULTS, ("g", "w", "dx"))
+_bwd_weight = cf.fake_args("mgs_conv3d_backward_weight", "mgs_conv3d_workspace_bytes", SHAPE, DEFAULTS,
+                           ("x", "g", "dw", "ws", "ws_bytes", "split"))
 
 
 def test_the_library_refuses_bad_arguments_before_any_launch():
@@ -101,20 +85,7 @@ def test_the_workspace_size_is_zero_for_illegal_shapes_and_follows_the_records_o
 
 
 def test_the_abi_version_is_still_17_and_the_header_matches_the_ctypes_table():
-    assert _lib.ABI_VERSION == 17 and _lib.lib().mgs_abi_version() == 17
-    hdr = open(os.path.join(ROOT, "include", "mgsplat.h")).read()
-    assert "#define MGS_ABI_VERSION 17" in re.sub(r"[ \t]+", " ", hdr)
-    declared = set(re.findall(r"\b(mgs_[a-z0-9_]+)\s*\(", hdr)) - {"mgs_stream_t"}
-    assert set(_lib.exported_symbols()) == declared
-    for name in ("mgs_conv3d_workspace_bytes", "mgs_conv3d_forward", "mgs_conv3d_backward_data", "mgs_conv3d_backward_weight"):
-        assert name in declared and hasattr(_lib.lib(), name), name
-    # the argument counts of the declarations and of the table agree
-    for name in declared:
-        if not name.startswith("mgs_conv3d_"):
-            continue
-        params = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", hdr, re.S).group(1)
-        assert len(params.split(",")) == len(getattr(_lib.lib(), name).argtypes), name
-    assert _lib.lib().mgs_conv3d_workspace_bytes.restype is ctypes.c_size_t
+    cf.check_abi(FAMILY.names)
 
 
 def test_the_ops_refuse_cpu_tensors_and_other_dtypes():
@@ -156,18 +127,6 @@ def test_a_cpu_stem_with_the_convolutions_forced_equals_torchs_composition_bit_f
     assert not enc._conv_routed(m.conv_out, xc, False)
 
 
-def _op_wins(entry):
-    """The criterion of encoder.fused_site(), for the convolutions: in all four (pass, form) pairs the op's third quartile lies below
-    the first quartile of torch's faster setting of cudnn.benchmark."""
-    for p in ("forward", "forward_backward"):
-        for f in ("eager", "graph"):
-            sides = entry[p][f]
-            t = min((sides["torch"], sides["torch_benchmark"]), key=lambda s: s["median_us"])
-            if not sides["op"]["q3_us"] < t["q1_us"]:
-                return False
-    return True
-
-
 def test_the_routing_rule_matches_the_committed_measurement():
     """profiles/conv3d_bench.json (scripts/bench_conv3d.py on an MI355X): conv_site() routes a site ONLY where the op won all four
     (pass, form) pairs, and nothing smaller than the smallest measured winner."""
@@ -176,7 +135,7 @@ def test_the_routing_rule_matches_the_committed_measurement():
     assert sorted(bench["sites"]) == sorted(STEM_SITES)
     routed, smallest = [], None
     for name, v in bench["sites"].items():
-        won = _op_wins(v)
+        won = cf.op_wins(v)
         assert won == v["op_wins"] == bench["routing_as_measured"][name], name
         rule = enc.conv_site(v["cin"], v["cout"], v["voxels"], v["stride"], v["transposed"])
         assert bench["routing_in_the_package"][name] == rule, name
@@ -204,106 +163,31 @@ def test_every_cases_yardstick_is_under_the_ceiling(case):
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------------
-def dev():
-    return torch.device("cuda:0")
-
-
-def run(case, t=None, split=0, x=None, w=None, g=None, need=(True, True)):
-    """{y, dx, dw}: CPU tensors of one forward + backward of the op on the case's inputs (or on x / w / g given, on the device)."""
-    t = cc.reference(case) if t is None else t
-    d = dev()
-    x = (t["x"].to(d) if x is None else x).detach().requires_grad_(need[0])
-    w = (t["w"].to(d) if w is None else w).detach().requires_grad_(need[1])
-    g = t["g"].to(d) if g is None else g
-    if cc.is_transposed(case):
-        y = cv._conv_transpose3d(x, w, cc.TRANSPOSED[case]["shape"][4], split)
-    else:
-        y = cv._conv3d(x, w, cc.CASES[case]["shape"][4], split)
-    y.backward(g)
-    torch.cuda.synchronize()
-    return {"y": y.detach().cpu(), "dx": None if x.grad is None else x.grad.cpu(), "dw": None if w.grad is None else w.grad.cpu()}
+dev = cf.dev
 
 
 @gpu
 @pytest.mark.parametrize("case", cc.ALL)
 def test_every_case_forward_and_both_gradients(case):
-    r = cc.reference(case)
-    got = run(case)
-    fails = []
-    for q in cc.QUANTITIES:
-        truth, yard = r[q + "64"], r["ref_err"][q]
-        assert yard <= cc.REF_ERR_CEILING, (case, q, yard)
-        assert got[q].shape == truth.shape and got[q].dtype == torch.float32, (case, q, got[q].shape)
-        e, bnd = (got[q].double() - truth).abs().max().item(), cc.bound(yard, truth)
-        print(f"{case} {q}: err {e:.3e}, bound {bnd:.3e} (yardstick {yard:.2e} of {truth.abs().max().item():.3e})")
-        if not e <= bnd:
-            fails.append((q, e, bnd))
-    assert not fails, (case, fails)
+    cf.check_case(FAMILY, case)
 
 
 @gpu
 @pytest.mark.parametrize("case", ["odd_s1", "down_even", "seam_tile_s2", "long_sum", "up_odd"])
 def test_the_same_bits_across_two_runs_and_across_splits(case):
-    want = run(case)
-    again = run(case)
-    for q in cc.QUANTITIES:
-        assert cc.same_bits(again[q], want[q]), (case, q, "second run")
-    for split in (1, 2, 7, 64):
-        got = run(case, split=split)
-        for q in cc.QUANTITIES:
-            assert cc.same_bits(got[q], want[q]), (case, q, split)
+    cf.check_same_bits(FAMILY, case)
 
 
 @gpu
 @pytest.mark.parametrize("case", ["down_mixed", "up_odd"])
 def test_only_the_requested_gradients_are_computed(case, monkeypatch):
-    L = _lib.lib()
-    calls = []
-    for name in ("mgs_conv3d_forward", "mgs_conv3d_backward_data", "mgs_conv3d_backward_weight"):
-        real = getattr(L, name)
-        monkeypatch.setattr(L, name, lambda *a, _real=real, _name=name: (calls.append(_name[len("mgs_conv3d_"):]), _real(*a))[1])
-    want = run(case)
-    first, data, weight = (("backward_data", "forward", "backward_weight") if cc.is_transposed(case) else
-                           ("forward", "backward_data", "backward_weight"))
-    assert calls == [first, data, weight]
-    del calls[:]
-    only_x = run(case, need=(True, False))
-    assert calls == [first, data] and only_x["dw"] is None and cc.same_bits(only_x["dx"], want["dx"])
-    del calls[:]
-    only_w = run(case, need=(False, True))
-    assert calls == [first, weight] and only_w["dx"] is None and cc.same_bits(only_w["dw"], want["dw"])
-    del calls[:]
-    r, d = cc.reference(case), dev()
-    op, last = (cv.conv_transpose3d, cc.TRANSPOSED[case]["shape"][4]) if cc.is_transposed(case) else (cv.conv3d, cc.CASES[case]["shape"][4])
-    with torch.no_grad():
-        y = op(r["x"].to(d), r["w"].to(d), last)
-    assert calls == [first] and cc.same_bits(y.cpu(), want["y"])
+    cf.check_requested_gradients(FAMILY, case, monkeypatch)
 
 
 @gpu
 @pytest.mark.parametrize("case", ["odd_s1", "up_odd"])
 def test_non_contiguous_and_offset_views_give_the_contiguous_result(case):
-    r = cc.reference(case)
-    want = run(case)
-    d = dev()
-
-    def channels_last(t):
-        v = t.to(d).permute(0, 2, 3, 4, 1).contiguous().permute(0, 4, 1, 2, 3)
-        assert not v.is_contiguous() and torch.equal(v, t.to(d))
-        return v
-
-    def shifted(t):
-        flat = torch.empty(t.numel() + 1, device=d)
-        v = flat[1:].view(t.shape)   # contiguous, 4 bytes off a 16-byte boundary
-        v.copy_(t)
-        assert v.is_contiguous() and v.data_ptr() % 16 == 4
-        return v
-
-    for tag, f in (("channels last", channels_last), ("4-byte offset", shifted)):
-        for which in ("x", "w", "g"):
-            got = run(case, **{which: f(r[which])})
-            for q in cc.QUANTITIES:
-                assert cc.same_bits(got[q], want[q]), (tag, which, q)
+    cf.check_views(FAMILY, case)
 
 
 @gpu
@@ -335,24 +219,14 @@ def test_the_stem_with_the_convolutions_routed_against_torchs_path(route):
     truth = once(False, torch.float64, "cpu")
     torchs = once(False, torch.float32, d)
     routed = once(True, torch.float32, d)
-    fails = []
-    for k, want in truth.items():
-        mag = want.abs().max().item()
-        yard = (torchs[k] - want).abs().max().item() / mag
-        e, bnd = (routed[k] - want).abs().max().item(), max(cc.FACTOR * yard, cc.FACTOR * cc.FLOOR) * mag
-        print(f"stem {k}: err {e:.3e}, bound {bnd:.3e} (torch's fp32 path {yard:.2e} of {mag:.3e})")
-        if not e <= bnd:
-            fails.append((k, e, bnd))
-    assert not fails, fails
+    cf.compare_modules("stem", "torch's fp32 path", truth, torchs, routed)
     assert any((routed[k] != torchs[k]).any() for k in routed), "the forced route changed nothing: the kernels did not run"
 
 
 @gpu
 def test_forward_and_backward_captured_into_a_hip_graph():
-    """In a child process: stream capture is process-wide state (tests/tools/conv3d_graph_capture_check.py)."""
-    tool = os.path.join(ROOT, "tests", "tools", "conv3d_graph_capture_check.py")
-    r = subprocess.run(["timeout", "-k", "10", "150", sys.executable, tool], capture_output=True, text=True, timeout=170)
-    assert r.returncode == 0 and "GRAPH_OK" in r.stdout, f"exit {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
+    """In a child process: stream capture is process-wide state (tests/tools/conv_graph_capture_check.py)."""
+    cf.graph_capture(FAMILY.name)
 
 
 @gpu

@@ -5,26 +5,24 @@ the truth, the float32 CPU run the yardstick,
 and two cases of small integers whose every sum is exact: bit-equal to the truth, which is what catches a dropped or misplaced tap
 (one term of 16 000 is below the float bound).
 """
-import ctypes
 import importlib
 import json
 import os
 import re
-import subprocess
-import sys
 
 import pytest
 import torch
 
+import conv_family as cf
 import dense_conv_cases as dc
-from manigaussian_amd import _lib, _ops
+from manigaussian_amd import _lib
 from manigaussian_amd import volume as vol
 
 dn = importlib.import_module("manigaussian_amd.dense")
 
 gpu = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ("mgs_dense_conv3d_workspace_bytes", "mgs_dense_conv3d_forward", "mgs_dense_conv3d_backward")
+ROOT = cf.ROOT
+FAMILY = cf.FAMILIES["dense"]
 BENCH_SHAPES = ("up0_first_20", "up0_last_100", "up0_last_50", "final_100", "final_50")
 SITES = {"up0_first": (256, 128, 5), "up0_last": (128, 128, 5), "final": (256, 128, 3)}
 
@@ -41,25 +39,14 @@ def switch():
 
 
 # ---- CPU ---------------------------------------------------------------------------------------------------------------------
-FAKE = 0x10000
+FAKE = cf.FAKE
 SHAPE = ("B", "Cin", "Cout", "k", "D", "H", "W")
-
-
-def _args(kw, names):
-    a = dict(B=1, Cin=8, Cout=32, k=3, D=5, H=6, W=7, slope=0.02, x=FAKE, y=FAKE, w=FAKE, bias=FAKE, g=FAKE, dx=FAKE, dw=FAKE, db=FAKE,
-             scratch=FAKE, ws=FAKE, ws_bytes=None, split=0)
-    a.update(kw)
-    if a["ws_bytes"] is None:
-        a["ws_bytes"] = max(_lib.lib().mgs_dense_conv3d_workspace_bytes(*(a[k] for k in SHAPE)), 256)
-    return [a[k] for k in SHAPE + names] + [None]
-
-
-def _fwd(**kw):
-    return _lib.lib().mgs_dense_conv3d_forward(*_args(kw, ("slope", "x", "w", "bias", "y", "ws", "ws_bytes")))
-
-
-def _bwd(**kw):
-    return _lib.lib().mgs_dense_conv3d_backward(*_args(kw, ("slope", "x", "y", "g", "w", "dx", "dw", "db", "scratch", "ws", "ws_bytes", "split")))
+DEFAULTS = dict(B=1, Cin=8, Cout=32, k=3, D=5, H=6, W=7, slope=0.02, x=FAKE, y=FAKE, w=FAKE, bias=FAKE, g=FAKE, dx=FAKE, dw=FAKE, db=FAKE,
+                scratch=FAKE, ws=FAKE)
+_fwd = cf.fake_args("mgs_dense_conv3d_forward", "mgs_dense_conv3d_workspace_bytes", SHAPE, DEFAULTS,
+                    ("slope", "x", "w", "bias", "y", "ws", "ws_bytes"))
+_bwd = cf.fake_args("mgs_dense_conv3d_backward", "mgs_dense_conv3d_workspace_bytes", SHAPE, DEFAULTS,
+                    ("slope", "x", "y", "g", "w", "dx", "dw", "db", "scratch", "ws", "ws_bytes", "split"))
 
 
 def test_the_library_refuses_bad_arguments_before_any_launch():
@@ -71,22 +58,9 @@ def test_the_library_refuses_bad_arguments_before_any_launch():
               (dict(H=0), "at least k"), (dict(W=-2), "at least k"), (dict(k=5, D=4), "at least k"),
               (dict(D=1 << 11, H=1 << 10, W=1 << 10), "2^31"), (dict(D=1289, H=1289, W=1289), "2^31"), (dict(W=1 << 40), "2^31"),
               (dict(B=1 << 40), "tiles"), (dict(B=65536), "tiles"), (dict(slope=float("nan")), "NaN"))
-    for kw, word in shapes:
-        for call in (_fwd, _bwd):
-            assert call(**kw) == INV, (call.__name__, kw)
-            assert word in _lib.last_error(), (call.__name__, kw, _lib.last_error())
-    for call, pointers in ((_fwd, ("x", "w", "y", "ws")), (_bwd, ("g", "y", "ws", "scratch"))):
-        for p in pointers:
-            assert call(**{p: None}) == INV and "NULL" in _lib.last_error(), (call.__name__, p, _lib.last_error())
-    for call, pointers in ((_fwd, ("x", "w", "bias", "y", "ws")), (_bwd, ("x", "y", "g", "w", "dx", "dw", "db", "scratch", "ws"))):
-        for p in pointers:
-            assert call(**{p: FAKE + 8}) == INV and "aligned" in _lib.last_error(), (call.__name__, p, _lib.last_error())
-    # what a gradient needs: w and the scratch for dx, x for dw; and one of the three has to be asked for
-    assert _bwd(w=None) == INV and "NULL" in _lib.last_error()
-    assert _bwd(x=None) == INV and "NULL" in _lib.last_error()
-    assert _bwd(dx=None, dw=None, db=None) == INV and "NULL" in _lib.last_error()
-    for split in (-1, 65):
-        assert _bwd(split=split) == INV and "split" in _lib.last_error()
+    # what a gradient needs beside these: w and the scratch for dx, x for dw; and one of the three has to be asked for
+    cf.check_refusals(_fwd, _bwd, shapes, required=(("x", "w", "y", "ws"), ("g", "y", "ws", "scratch")),
+                      pointers=(("x", "w", "bias", "y", "ws"), ("x", "y", "g", "w", "dx", "dw", "db", "scratch", "ws")))
     need = _lib.lib().mgs_dense_conv3d_workspace_bytes(1, 8, 32, 3, 5, 6, 7)
     for call in (_fwd, _bwd):
         assert call(ws_bytes=need - 1) == _lib.MGS_ERR_WORKSPACE and "needed" in _lib.last_error()
@@ -124,16 +98,7 @@ def test_the_workspace_size_is_zero_for_illegal_shapes_and_follows_the_records_o
 
 
 def test_the_abi_version_is_still_17_and_the_new_names_match_the_ctypes_table():
-    assert _lib.ABI_VERSION == 17 and _lib.lib().mgs_abi_version() == 17
-    hdr = open(os.path.join(ROOT, "include", "mgsplat.h")).read()
-    assert "#define MGS_ABI_VERSION 17" in re.sub(r"[ \t]+", " ", hdr)
-    declared = set(re.findall(r"\b(mgs_[a-z0-9_]+)\s*\(", hdr)) - {"mgs_stream_t"}
-    assert set(_lib.exported_symbols()) == declared
-    for name in NAMES:
-        assert name in declared and hasattr(_lib.lib(), name), name
-        params = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", hdr, re.S).group(1)
-        assert len(params.split(",")) == len(getattr(_lib.lib(), name).argtypes), name
-    assert _lib.lib().mgs_dense_conv3d_workspace_bytes.restype is ctypes.c_size_t
+    cf.check_abi(FAMILY.names)
 
 
 def test_the_op_refuses_cpu_tensors_other_dtypes_and_bad_shapes():
@@ -197,19 +162,6 @@ def test_the_seam_cases_straddle_the_kernels_tiles():
                                                                                                     ("final", "up0_last", "up0_first")]
 
 
-def _op_wins(entry):
-    """The criterion of encoder.fused_site(): in all four (pass, form) pairs the op's third quartile lies below the first quartile of
-    torch's faster setting of cudnn.benchmark (a torch_benchmark child that did not finish is recorded as such and not compared)."""
-    for p in ("forward", "forward_backward"):
-        for f in ("eager", "graph"):
-            sides = entry[p][f]
-            ts = [sides[s] for s in ("torch", "torch_benchmark") if s in sides and "median_us" in sides[s]]
-            t = min(ts, key=lambda s: s["median_us"])
-            if not sides["op"]["q3_us"] < t["q1_us"]:
-                return False
-    return True
-
-
 def test_the_routing_rule_matches_the_committed_measurement():
     """profiles/dense_conv_bench.json (scripts/bench_dense.py on an MI355X): dense_site() routes a shape ONLY where the op won all four
     (pass, form) pairs, and nothing smaller than the smallest measured winner of its channel counts or at channel counts nobody
@@ -219,7 +171,7 @@ def test_the_routing_rule_matches_the_committed_measurement():
     assert sorted(bench["shapes"]) == sorted(BENCH_SHAPES)
     routed, smallest = [], {}
     for name, v in bench["shapes"].items():
-        won = _op_wins(v)
+        won = cf.op_wins(v, benchmark_may_be_missing=True)   # (the file records torch_benchmark children that did not finish)
         assert won == v["op_wins"] == bench["routing_as_measured"][name], name
         key = (v["cin"], v["cout"], v["k"])
         assert key == SITES[name.rsplit("_", 1)[0]] and v["voxels"] == v["side"] ** 3 and v["side"] == int(name.rsplit("_", 1)[1])
@@ -278,60 +230,20 @@ def test_a_cpu_block_is_todays_result_bit_for_bit_whatever_the_switch(switch):
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------------
-def dev():
-    return torch.device("cuda:0")
-
-
-def run(case, split=0, x=None, w=None, b=None, g=None, need=(True, True, True)):
-    """{y, dx, dw, db}: CPU tensors of one forward + backward of the op on the case's inputs (or on x / w / b / g given, on the device)."""
-    t = dc.reference(case)
-    d = dev()
-    x = (t["x"].to(d) if x is None else x).detach().requires_grad_(need[0])
-    w = (t["w"].to(d) if w is None else w).detach().requires_grad_(need[1])
-    if t["b"] is None:
-        b = None
-    else:
-        b = (t["b"].to(d) if b is None else b).detach().requires_grad_(need[2])
-    g = t["g"].to(d) if g is None else g
-    y = dn._dense_conv3d(x, w, b, dc.slope_of(case), split)
-    assert y.is_contiguous()
-    if y.requires_grad:
-        y.backward(g)
-    torch.cuda.synchronize()
-
-    def grad(v):
-        if v is None or v.grad is None:
-            return None
-        # (autograd lays the .grad of a non-contiguous leaf out like the leaf: what the op returned is seen where the leaf is contiguous)
-        assert v.grad.is_contiguous() or not v.is_contiguous()
-        return v.grad.cpu()
-    return {"y": y.detach().cpu(), "dx": grad(x), "dw": grad(w), "db": grad(b)}
+dev = cf.dev
 
 
 @gpu
 @pytest.mark.parametrize("case", dc.ALL)
 def test_every_case_forward_and_all_gradients(case):
-    r = dc.reference(case)
-    got = run(case)
-    fails = []
-    for q in dc.quantities(case):
-        truth, yard = r[q + "64"], r["ref_err"][q]
-        assert yard <= dc.REF_ERR_CEILING, (case, q, yard)
-        assert got[q].shape == truth.shape and got[q].dtype == torch.float32, (case, q, got[q].shape)
-        e, bnd = (got[q].double() - truth).abs().max().item(), dc.bound(yard, truth)
-        print(f"{case} {q}: err {e:.3e}, bound {bnd:.3e} (yardstick {yard:.2e} of {truth.abs().max().item():.3e})")
-        if not e <= bnd:
-            fails.append((q, e, bnd))
-    assert not fails, (case, fails)
-    if not dc.has_bias(case):
-        assert got["db"] is None
+    cf.check_case(FAMILY, case)
 
 
 @gpu
 @pytest.mark.parametrize("case", list(dc.EXACT))
 def test_the_exact_cases_are_bit_equal_to_the_truth(case):
     r = dc.reference(case)
-    got = run(case)
+    got = cf.run(FAMILY, case)
     for q in ("y", "dx", "dw", "db"):
         truth = r[q + "64"]
         wrong = int((got[q].double() != truth).sum())
@@ -342,96 +254,19 @@ def test_the_exact_cases_are_bit_equal_to_the_truth(case):
 @gpu
 @pytest.mark.parametrize("case", ["odd_k3", "seams", "long_sum", "long_sum_head"])
 def test_the_same_bits_across_two_runs_and_across_splits(case):
-    want = run(case)
-    again = run(case)
-    for q in dc.quantities(case):
-        assert dc.same_bits(again[q], want[q]), (case, q, "second run")
-    for split in (1, 3, 64):
-        got = run(case, split=split)
-        for q in dc.quantities(case):
-            assert dc.same_bits(got[q], want[q]), (case, q, split)
-
-
-def _count_calls(monkeypatch):
-    """Replaces the two entry points on the library object by wrappers that record (name, dx, dw, db, scratch given) per call."""
-    L = _lib.lib()
-    calls = []
-
-    def wrap(name, real):
-        def f(*a):
-            calls.append((name[len("mgs_dense_conv3d_"):],) + (tuple(bool(p) for p in a[12:16]) if name.endswith("backward") else ()))
-            return real(*a)
-        return f
-    for name in ("mgs_dense_conv3d_forward", "mgs_dense_conv3d_backward"):
-        monkeypatch.setattr(L, name, wrap(name, getattr(L, name)))
-    return calls
+    cf.check_same_bits(FAMILY, case)
 
 
 @gpu
 @pytest.mark.parametrize("case", ["odd_k3", "odd_k5", "plain"])
 def test_only_the_requested_gradients_are_computed(case, monkeypatch):
-    calls = _count_calls(monkeypatch)
-    want = run(case)
-    assert calls == [("forward",), ("backward", True, True, True, True)]
-    del calls[:]
-    only_x = run(case, need=(True, False, False))
-    assert calls == [("forward",), ("backward", True, False, False, True)], "dx alone: dw and db are passed as null"
-    assert only_x["dw"] is None and only_x["db"] is None and dc.same_bits(only_x["y"], want["y"])
-    assert dc.same_bits(only_x["dx"], want["dx"])
-    r = dc.reference(case)
-    del calls[:]
-    only_wb = run(case, need=(False, True, True))
-    assert calls == [("forward",), ("backward", False, True, True, False)], "no dx: no padded gradient is allocated"
-    assert only_wb["dx"] is None and dc.same_bits(only_wb["dw"], want["dw"]) and dc.same_bits(only_wb["db"], want["db"])
-    del calls[:]
-    only_b = run(case, need=(False, False, True))
-    assert calls == [("forward",), ("backward", False, False, True, False)]
-    assert only_b["dx"] is None and only_b["dw"] is None and dc.same_bits(only_b["db"], want["db"])
-    del calls[:]
-    x_and_w = run(case, need=(True, True, False))
-    assert calls == [("forward",), ("backward", True, True, False, True)]
-    assert x_and_w["db"] is None and dc.same_bits(x_and_w["dx"], want["dx"]) and dc.same_bits(x_and_w["dw"], want["dw"])
-    del calls[:]
-    d = dev()
-    with torch.no_grad():
-        y = dn.dense_conv3d(r["x"].to(d), r["w"].to(d), r["b"].to(d), dc.slope_of(case))
-    assert calls == [("forward",)] and dc.same_bits(y.cpu(), want["y"])
-    del calls[:]
-    none = run(case, need=(False, False, False))
-    assert calls == [("forward",)] and dc.same_bits(none["y"], want["y"])
+    """dx alone: dw and db are passed as null; no dx: no padded gradient is allocated."""
+    cf.check_requested_gradients(FAMILY, case, monkeypatch)
 
 
 @gpu
 def test_non_contiguous_and_offset_views_give_the_contiguous_result():
-    case = "odd_k3"
-    r = dc.reference(case)
-    want = run(case)
-    d = dev()
-
-    def channels_last(t):
-        v = t.to(d).permute(0, 2, 3, 4, 1).contiguous().permute(0, 4, 1, 2, 3)
-        assert not v.is_contiguous() and torch.equal(v, t.to(d))
-        return v
-
-    def strided(t):   # (a [Cout] bias has no channels-last form: every other element of a longer vector)
-        v = torch.empty(2 * t.numel(), device=d)[::2].view(t.shape)
-        v.copy_(t)
-        assert not v.is_contiguous() and torch.equal(v, t.to(d))
-        return v
-
-    def shifted(t):
-        flat = torch.empty(t.numel() + 1, device=d)
-        v = flat[1:].view(t.shape)   # contiguous, 4 bytes off a 16-byte boundary
-        v.copy_(t)
-        assert v.is_contiguous() and v.data_ptr() % 16 == 4
-        return v
-
-    for tag, f in (("channels last", channels_last), ("4-byte offset", shifted)):
-        for which in ("x", "w", "b", "g"):
-            view = strided(r[which]) if (which == "b" and f is channels_last) else f(r[which])
-            got = run(case, **{which: view})
-            for q in dc.quantities(case):
-                assert dc.same_bits(got[q], want[q]), (tag, which, q)
+    cf.check_views(FAMILY, "odd_k3")
 
 
 def _float64(module, x):
@@ -469,7 +304,7 @@ def test_the_block_routed_against_the_same_module_not_routed(which, switch, monk
     gen = torch.Generator().manual_seed(92)
     x = torch.randn(1, cin, *ext, generator=gen).to(d)
     g = torch.randn(1, 128, *out_ext, generator=gen).to(d)
-    calls = _count_calls(monkeypatch)
+    calls = cf.count_calls(monkeypatch, FAMILY)
 
     def once(dense, dtype, where):
         switch(dense)
@@ -489,15 +324,7 @@ def test_the_block_routed_against_the_same_module_not_routed(which, switch, monk
     assert calls == [], "DENSE = False: the module's own convolution"
     routed = once(True, torch.float32, d)
     assert calls == [("forward",)] * n + [("backward", True, True, True, True)] * n, calls
-    fails = []
-    for k, want in truth.items():
-        mag = want.abs().max().item()
-        yard = (torchs[k] - want).abs().max().item() / mag
-        e, bnd = (routed[k] - want).abs().max().item(), max(dc.FACTOR * yard, dc.FACTOR * dc.FLOOR) * mag
-        print(f"block {which} {k}: err {e:.3e}, bound {bnd:.3e} (the module's fp32 path {yard:.2e} of {mag:.3e})")
-        if not e <= bnd:
-            fails.append((k, e, bnd))
-    assert not fails, fails
+    cf.compare_modules(f"block {which}", "the module's fp32 path", truth, torchs, routed)
     # under the rule these toy shapes take today's path: the existing tests run the code they ran before
     del calls[:]
     once(None, torch.float32, d)
@@ -508,7 +335,7 @@ def test_the_block_routed_against_the_same_module_not_routed(which, switch, monk
 def test_a_block_without_padding_and_one_with_another_activation_reach_the_op(switch, monkeypatch):
     d = dev()
     torch.manual_seed(93)
-    calls = _count_calls(monkeypatch)
+    calls = cf.count_calls(monkeypatch, FAMILY)
     x = torch.randn(1, 8, 5, 6, 7, generator=torch.Generator().manual_seed(94)).to(d)
     for activation, padding in (("relu", 0), ("tanh", None), (None, 0)):
         m = vol.Conv3DBlock(8, 32, kernel_sizes=3, strides=1, norm=None, activation=activation, padding=padding).to(d)
@@ -525,10 +352,8 @@ def test_a_block_without_padding_and_one_with_another_activation_reach_the_op(sw
 
 @gpu
 def test_forward_and_backward_captured_into_a_hip_graph():
-    """In a child process: stream capture is process-wide state (tests/tools/dense_graph_capture_check.py)."""
-    tool = os.path.join(ROOT, "tests", "tools", "dense_graph_capture_check.py")
-    r = subprocess.run(["timeout", "-k", "10", "150", sys.executable, tool], capture_output=True, text=True, timeout=170)
-    assert r.returncode == 0 and "GRAPH_OK" in r.stdout, f"exit {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
+    """In a child process: stream capture is process-wide state (tests/tools/conv_graph_capture_check.py)."""
+    cf.graph_capture(FAMILY.name)
 
 
 @gpu

@@ -4,17 +4,15 @@ the float32 CPU run the yardstick,
     |ours - truth| <= 16 x max(yardstick, 2^-23) x max|truth|    for y, dx, dw and db of every case,
 and one case of small integers whose every sum is exact: bit-equal to the truth.
 """
-import ctypes
 import importlib
 import json
 import os
 import re
-import subprocess
-import sys
 
 import pytest
 import torch
 
+import conv_family as cf
 import narrow_conv_cases as nc
 from manigaussian_amd import _lib, _ops
 from manigaussian_amd import volume as vol
@@ -22,8 +20,8 @@ from manigaussian_amd import volume as vol
 nw = importlib.import_module("manigaussian_amd.narrow")
 
 gpu = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ("mgs_narrow_conv3d_workspace_bytes", "mgs_narrow_conv3d_forward", "mgs_narrow_conv3d_backward")
+ROOT = cf.ROOT
+FAMILY = cf.FAMILIES["narrow"]
 BENCH_SHAPES = ("trans_decoder_100", "trans_decoder_50", "trans_decoder_25")
 
 
@@ -39,25 +37,12 @@ def switch():
 
 
 # ---- CPU ---------------------------------------------------------------------------------------------------------------------
-FAKE = 0x10000
+FAKE = cf.FAKE
 SHAPE = ("B", "Cin", "Cout", "D", "H", "W", "zeros")
-
-
-def _args(kw, names):
-    a = dict(B=1, Cin=4, Cout=2, D=5, H=6, W=7, zeros=0, x=FAKE, w=FAKE, bias=FAKE, y=FAKE, g=FAKE, dx=FAKE, dw=FAKE, db=FAKE, ws=FAKE,
-             ws_bytes=None, split=0)
-    a.update(kw)
-    if a["ws_bytes"] is None:
-        a["ws_bytes"] = max(_lib.lib().mgs_narrow_conv3d_workspace_bytes(*(a[k] for k in SHAPE[:6])), 256)
-    return [a[k] for k in SHAPE + names] + [None]
-
-
-def _fwd(**kw):
-    return _lib.lib().mgs_narrow_conv3d_forward(*_args(kw, ("x", "w", "bias", "y")))
-
-
-def _bwd(**kw):
-    return _lib.lib().mgs_narrow_conv3d_backward(*_args(kw, ("x", "g", "w", "dx", "dw", "db", "ws", "ws_bytes", "split")))
+DEFAULTS = dict(B=1, Cin=4, Cout=2, D=5, H=6, W=7, zeros=0, x=FAKE, w=FAKE, bias=FAKE, y=FAKE, g=FAKE, dx=FAKE, dw=FAKE, db=FAKE, ws=FAKE)
+_fwd = cf.fake_args("mgs_narrow_conv3d_forward", "mgs_narrow_conv3d_workspace_bytes", SHAPE, DEFAULTS, ("x", "w", "bias", "y"), SHAPE[:6])
+_bwd = cf.fake_args("mgs_narrow_conv3d_backward", "mgs_narrow_conv3d_workspace_bytes", SHAPE, DEFAULTS,
+                    ("x", "g", "w", "dx", "dw", "db", "ws", "ws_bytes", "split"), SHAPE[:6])
 
 
 def test_the_library_refuses_bad_arguments_before_any_launch():
@@ -67,22 +52,9 @@ def test_the_library_refuses_bad_arguments_before_any_launch():
               (dict(Cout=-1), "1 to 4"), (dict(B=0), "at least 1"), (dict(B=-3), "at least 1"), (dict(D=0), "at least 1"),
               (dict(H=0), "at least 1"), (dict(W=-2), "at least 1"), (dict(D=1 << 11, H=1 << 10, W=1 << 10), "2^31"),
               (dict(W=1 << 40), "2^31"), (dict(B=1 << 40), "tiles"), (dict(zeros=2), "zeros_pad"), (dict(zeros=-1), "zeros_pad"))
-    for kw, word in shapes:
-        for call in (_fwd, _bwd):
-            assert call(**kw) == INV, (call.__name__, kw)
-            assert word in _lib.last_error(), (call.__name__, kw, _lib.last_error())
-    for call, pointers in ((_fwd, ("x", "w", "y")), (_bwd, ("g", "ws"))):
-        for p in pointers:
-            assert call(**{p: None}) == INV and "NULL" in _lib.last_error(), (call.__name__, p, _lib.last_error())
-    for call, pointers in ((_fwd, ("x", "w", "bias", "y")), (_bwd, ("x", "g", "w", "dx", "dw", "db", "ws"))):
-        for p in pointers:
-            assert call(**{p: FAKE + 8}) == INV and "aligned" in _lib.last_error(), (call.__name__, p, _lib.last_error())
-    # what a gradient needs: w for dx, x for dw; and one of the three has to be asked for
-    assert _bwd(w=None) == INV and "NULL" in _lib.last_error()
-    assert _bwd(x=None) == INV and "NULL" in _lib.last_error()
-    assert _bwd(dx=None, dw=None, db=None) == INV and "NULL" in _lib.last_error()
-    for split in (-1, 65):
-        assert _bwd(split=split) == INV and "split" in _lib.last_error()
+    # what a gradient needs beside these: w for dx, x for dw; and one of the three has to be asked for
+    cf.check_refusals(_fwd, _bwd, shapes, required=(("x", "w", "y"), ("g", "ws")),
+                      pointers=(("x", "w", "bias", "y"), ("x", "g", "w", "dx", "dw", "db", "ws")))
     need = _lib.lib().mgs_narrow_conv3d_workspace_bytes(1, 4, 2, 5, 6, 7)
     assert _bwd(ws_bytes=need - 1) == _lib.MGS_ERR_WORKSPACE and "needed" in _lib.last_error()
     assert _bwd(dw=None, db=None, ws_bytes=need - 1, split=65) == INV, "the split is checked even where dx alone is asked for"
@@ -107,16 +79,7 @@ def test_the_workspace_size_is_zero_for_illegal_shapes_and_follows_the_records_o
 
 
 def test_the_abi_version_is_still_17_and_the_new_names_match_the_ctypes_table():
-    assert _lib.ABI_VERSION == 17 and _lib.lib().mgs_abi_version() == 17
-    hdr = open(os.path.join(ROOT, "include", "mgsplat.h")).read()
-    assert "#define MGS_ABI_VERSION 17" in re.sub(r"[ \t]+", " ", hdr)
-    declared = set(re.findall(r"\b(mgs_[a-z0-9_]+)\s*\(", hdr)) - {"mgs_stream_t"}
-    assert set(_lib.exported_symbols()) == declared
-    for name in NAMES:
-        assert name in declared and hasattr(_lib.lib(), name), name
-        params = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", hdr, re.S).group(1)
-        assert len(params.split(",")) == len(getattr(_lib.lib(), name).argtypes), name
-    assert _lib.lib().mgs_narrow_conv3d_workspace_bytes.restype is ctypes.c_size_t
+    cf.check_abi(FAMILY.names)
 
 
 def test_the_op_refuses_cpu_tensors_other_dtypes_and_bad_shapes():
@@ -157,18 +120,6 @@ def test_every_cases_yardstick_is_under_the_ceiling(case):
         assert r["ref_err"][q] <= nc.REF_ERR_CEILING, (case, q, r["ref_err"][q])
 
 
-def _op_wins(entry):
-    """The criterion of encoder.fused_site(): in all four (pass, form) pairs the op's third quartile lies below the first quartile of
-    torch's faster setting of cudnn.benchmark."""
-    for p in ("forward", "forward_backward"):
-        for f in ("eager", "graph"):
-            sides = entry[p][f]
-            t = min((sides["torch"], sides["torch_benchmark"]), key=lambda s: s["median_us"])
-            if not sides["op"]["q3_us"] < t["q1_us"]:
-                return False
-    return True
-
-
 def test_the_routing_rule_matches_the_committed_measurement():
     """profiles/narrow_conv_bench.json (scripts/bench_narrow.py on an MI355X): narrow_site() routes a shape ONLY where the op won all
     four (pass, form) pairs, and nothing smaller than the smallest measured winner or at channel counts nobody measured."""
@@ -177,7 +128,7 @@ def test_the_routing_rule_matches_the_committed_measurement():
     assert sorted(bench["shapes"]) == sorted(BENCH_SHAPES)
     routed, smallest = [], None
     for name, v in bench["shapes"].items():
-        won = _op_wins(v)
+        won = cf.op_wins(v)
         assert won == v["op_wins"] == bench["routing_as_measured"][name], name
         assert (v["cin"], v["cout"]) == (128, 1) and v["voxels"] == v["side"] ** 3
         rule = vol.narrow_site(v["cin"], v["cout"], v["voxels"])
@@ -228,59 +179,19 @@ def test_a_cpu_block_is_todays_result_bit_for_bit_whatever_the_switch(switch):
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------------
-def dev():
-    return torch.device("cuda:0")
-
-
-def run(case, split=0, x=None, w=None, b=None, g=None, need=(True, True, True)):
-    """{y, dx, dw, db}: CPU tensors of one forward + backward of the op on the case's inputs (or on x / w / b / g given, on the device)."""
-    t = nc.reference(case)
-    d = dev()
-    x = (t["x"].to(d) if x is None else x).detach().requires_grad_(need[0])
-    w = (t["w"].to(d) if w is None else w).detach().requires_grad_(need[1])
-    if t["b"] is None:
-        b = None
-    else:
-        b = (t["b"].to(d) if b is None else b).detach().requires_grad_(need[2])
-    g = t["g"].to(d) if g is None else g
-    y = nw._narrow_conv3d(x, w, b, "replicate" if case == "exact" else nc.mode_of(case), split)
-    assert y.is_contiguous()
-    if y.requires_grad:
-        y.backward(g)
-    torch.cuda.synchronize()
-
-    def grad(v):
-        if v is None or v.grad is None:
-            return None
-        # (autograd lays the .grad of a non-contiguous leaf out like the leaf: what the op returned is seen where the leaf is contiguous)
-        assert v.grad.is_contiguous() or not v.is_contiguous()
-        return v.grad.cpu()
-    return {"y": y.detach().cpu(), "dx": grad(x), "dw": grad(w), "db": grad(b)}
+dev = cf.dev
 
 
 @gpu
 @pytest.mark.parametrize("case", nc.ALL)
 def test_every_case_forward_and_all_gradients(case):
-    r = nc.reference(case)
-    got = run(case)
-    fails = []
-    for q in nc.quantities(case):
-        truth, yard = r[q + "64"], r["ref_err"][q]
-        assert yard <= nc.REF_ERR_CEILING, (case, q, yard)
-        assert got[q].shape == truth.shape and got[q].dtype == torch.float32, (case, q, got[q].shape)
-        e, bnd = (got[q].double() - truth).abs().max().item(), nc.bound(yard, truth)
-        print(f"{case} {q}: err {e:.3e}, bound {bnd:.3e} (yardstick {yard:.2e} of {truth.abs().max().item():.3e})")
-        if not e <= bnd:
-            fails.append((q, e, bnd))
-    assert not fails, (case, fails)
-    if not nc.has_bias(case):
-        assert got["db"] is None
+    cf.check_case(FAMILY, case)
 
 
 @gpu
 def test_the_exact_case_is_bit_equal_to_the_truth():
     r = nc.reference("exact")
-    got = run("exact")
+    got = cf.run(FAMILY, "exact")
     for q in ("y", "dx", "dw", "db"):
         truth = r[q + "64"]
         wrong = int((got[q].double() != truth).sum())
@@ -291,96 +202,19 @@ def test_the_exact_case_is_bit_equal_to_the_truth():
 @gpu
 @pytest.mark.parametrize("case", ["odd", "seams", "long_sum", "long_sum_head"])
 def test_the_same_bits_across_two_runs_and_across_splits(case):
-    want = run(case)
-    again = run(case)
-    for q in nc.quantities(case):
-        assert nc.same_bits(again[q], want[q]), (case, q, "second run")
-    for split in (1, 3, 64):
-        got = run(case, split=split)
-        for q in nc.quantities(case):
-            assert nc.same_bits(got[q], want[q]), (case, q, split)
-
-
-def _count_calls(monkeypatch):
-    """Replaces the two entry points on the library object by wrappers that record (name, dx, dw, db, workspace given) per call."""
-    L = _lib.lib()
-    calls = []
-
-    def wrap(name, real):
-        def f(*a):
-            calls.append((name[len("mgs_narrow_conv3d_"):],) + (tuple(bool(p) for p in a[10:14]) if name.endswith("backward") else ()))
-            return real(*a)
-        return f
-    for name in ("mgs_narrow_conv3d_forward", "mgs_narrow_conv3d_backward"):
-        monkeypatch.setattr(L, name, wrap(name, getattr(L, name)))
-    return calls
+    cf.check_same_bits(FAMILY, case)
 
 
 @gpu
 @pytest.mark.parametrize("case", ["odd", "odd_zeros", "wide_in"])
 def test_only_the_requested_gradients_are_computed(case, monkeypatch):
-    calls = _count_calls(monkeypatch)
-    want = run(case)
-    assert calls == [("forward",), ("backward", True, True, True, True)]
-    del calls[:]
-    only_x = run(case, need=(True, False, False))
-    assert calls == [("forward",), ("backward", True, False, False, False)], "dx alone: dw, db and the workspace are passed as null"
-    assert only_x["dw"] is None and only_x["db"] is None and nc.same_bits(only_x["y"], want["y"])
-    assert nc.same_bits(only_x["dx"], want["dx"])
-    r = nc.reference(case)
-    del calls[:]
-    only_wb = run(case, need=(False, True, True))
-    assert calls == [("forward",), ("backward", False, True, True, True)]
-    assert only_wb["dx"] is None and nc.same_bits(only_wb["dw"], want["dw"]) and nc.same_bits(only_wb["db"], want["db"])
-    del calls[:]
-    only_b = run(case, need=(False, False, True))
-    assert calls == [("forward",), ("backward", False, False, True, True)]
-    assert only_b["dx"] is None and only_b["dw"] is None and nc.same_bits(only_b["db"], want["db"])
-    del calls[:]
-    x_and_w = run(case, need=(True, True, False))
-    assert calls == [("forward",), ("backward", True, True, False, True)]
-    assert x_and_w["db"] is None and nc.same_bits(x_and_w["dx"], want["dx"]) and nc.same_bits(x_and_w["dw"], want["dw"])
-    del calls[:]
-    d = dev()
-    with torch.no_grad():
-        y = nw.narrow_conv3d(r["x"].to(d), r["w"].to(d), r["b"].to(d), nc.mode_of(case))
-    assert calls == [("forward",)] and nc.same_bits(y.cpu(), want["y"])
-    del calls[:]
-    none = run(case, need=(False, False, False))
-    assert calls == [("forward",)] and nc.same_bits(none["y"], want["y"])
+    """dx alone: dw, db and the workspace are passed as null."""
+    cf.check_requested_gradients(FAMILY, case, monkeypatch)
 
 
 @gpu
 def test_non_contiguous_and_offset_views_give_the_contiguous_result():
-    case = "odd"
-    r = nc.reference(case)
-    want = run(case)
-    d = dev()
-
-    def channels_last(t):
-        v = t.to(d).permute(0, 2, 3, 4, 1).contiguous().permute(0, 4, 1, 2, 3)
-        assert not v.is_contiguous() and torch.equal(v, t.to(d))
-        return v
-
-    def strided(t):   # (a [Cout] bias has no channels-last form: every other element of a longer vector)
-        v = torch.empty(2 * t.numel(), device=d)[::2].view(t.shape)
-        v.copy_(t)
-        assert not v.is_contiguous() and torch.equal(v, t.to(d))
-        return v
-
-    def shifted(t):
-        flat = torch.empty(t.numel() + 1, device=d)
-        v = flat[1:].view(t.shape)   # contiguous, 4 bytes off a 16-byte boundary
-        v.copy_(t)
-        assert v.is_contiguous() and v.data_ptr() % 16 == 4
-        return v
-
-    for tag, f in (("channels last", channels_last), ("4-byte offset", shifted)):
-        for which in ("x", "w", "b", "g"):
-            view = strided(r[which]) if (which == "b" and f is channels_last) else f(r[which])
-            got = run(case, **{which: view})
-            for q in nc.quantities(case):
-                assert nc.same_bits(got[q], want[q]), (tag, which, q)
+    cf.check_views(FAMILY, "odd")
 
 
 @gpu
@@ -398,7 +232,7 @@ def test_the_block_routed_against_the_same_module_not_routed(cout, activation, s
     gen = torch.Generator().manual_seed(72)
     x = torch.randn(1, 128, 6, 7, 8, generator=gen).to(d)
     g = torch.randn(1, cout, 6, 7, 8, generator=gen).to(d)
-    calls = _count_calls(monkeypatch)
+    calls = cf.count_calls(monkeypatch, FAMILY)
     pads = []
     real_call = _ops.call
 
@@ -433,15 +267,7 @@ def test_the_block_routed_against_the_same_module_not_routed(cout, activation, s
     routed = once(True, torch.float32, d)
     assert calls == [("forward",), ("backward", True, True, True, True)], calls
     assert pads == [], "NARROW = True: the input is not padded first"
-    fails = []
-    for k, want in truth.items():
-        mag = want.abs().max().item()
-        yard = (torchs[k] - want).abs().max().item() / mag
-        e, bnd = (routed[k] - want).abs().max().item(), max(nc.FACTOR * yard, nc.FACTOR * nc.FLOOR) * mag
-        print(f"block {cout} {k}: err {e:.3e}, bound {bnd:.3e} (the module's fp32 path {yard:.2e} of {mag:.3e})")
-        if not e <= bnd:
-            fails.append((k, e, bnd))
-    assert not fails, fails
+    cf.compare_modules(f"block {cout}", "the module's fp32 path", truth, torchs, routed)
     # a list input still takes the old path, and so does this shape under the rule: the existing tests run the code they ran before
     del calls[:], pads[:]
     once(True, torch.float32, d, as_list=True)
@@ -453,10 +279,8 @@ def test_the_block_routed_against_the_same_module_not_routed(cout, activation, s
 
 @gpu
 def test_forward_and_backward_captured_into_a_hip_graph():
-    """In a child process: stream capture is process-wide state (tests/tools/narrow_graph_capture_check.py)."""
-    tool = os.path.join(ROOT, "tests", "tools", "narrow_graph_capture_check.py")
-    r = subprocess.run(["timeout", "-k", "10", "150", sys.executable, tool], capture_output=True, text=True, timeout=170)
-    assert r.returncode == 0 and "GRAPH_OK" in r.stdout, f"exit {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
+    """In a child process: stream capture is process-wide state (tests/tools/conv_graph_capture_check.py)."""
+    cf.graph_capture(FAMILY.name)
 
 
 @gpu

@@ -2,17 +2,15 @@
 against torch's own F.conv3d on the CPU (tests/pointwise_cases.py): float64 is the truth, the float32 CPU run the yardstick,
     |ours - truth| <= 16 x max(yardstick, 2^-23) x max|truth|    for y, dx, dw and db of every case.
 """
-import ctypes
 import importlib
 import json
 import os
 import re
-import subprocess
-import sys
 
 import pytest
 import torch
 
+import conv_family as cf
 import pointwise_cases as pc
 from manigaussian_amd import _lib
 from manigaussian_amd import encoder as enc
@@ -20,8 +18,8 @@ from manigaussian_amd import encoder as enc
 pw = importlib.import_module("manigaussian_amd.pointwise")
 
 gpu = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ("mgs_pointwise_workspace_bytes", "mgs_pointwise_forward", "mgs_pointwise_backward")
+ROOT = cf.ROOT
+FAMILY = cf.FAMILIES["pointwise"]
 BENCH_SHAPES = ("conv_out_100", "conv_out_50", "conv_out_25")
 
 
@@ -37,25 +35,12 @@ def switches():
 
 
 # ---- CPU ---------------------------------------------------------------------------------------------------------------------
-FAKE = 0x10000
+FAKE = cf.FAKE
 SHAPE = ("B", "Cin", "Cout", "n")
-
-
-def _args(kw, names):
-    a = dict(B=1, Cin=4, Cout=8, n=210, x=FAKE, w=FAKE, bias=FAKE, y=FAKE, g=FAKE, dx=FAKE, dw=FAKE, db=FAKE, ws=FAKE, ws_bytes=None,
-             split=0)
-    a.update(kw)
-    if a["ws_bytes"] is None:
-        a["ws_bytes"] = max(_lib.lib().mgs_pointwise_workspace_bytes(*(a[k] for k in SHAPE)), 256)
-    return [a[k] for k in SHAPE + names] + [None]
-
-
-def _fwd(**kw):
-    return _lib.lib().mgs_pointwise_forward(*_args(kw, ("x", "w", "bias", "y")))
-
-
-def _bwd(**kw):
-    return _lib.lib().mgs_pointwise_backward(*_args(kw, ("x", "g", "w", "dx", "dw", "db", "ws", "ws_bytes", "split")))
+DEFAULTS = dict(B=1, Cin=4, Cout=8, n=210, x=FAKE, w=FAKE, bias=FAKE, y=FAKE, g=FAKE, dx=FAKE, dw=FAKE, db=FAKE, ws=FAKE)
+_fwd = cf.fake_args("mgs_pointwise_forward", "mgs_pointwise_workspace_bytes", SHAPE, DEFAULTS, ("x", "w", "bias", "y"))
+_bwd = cf.fake_args("mgs_pointwise_backward", "mgs_pointwise_workspace_bytes", SHAPE, DEFAULTS,
+                    ("x", "g", "w", "dx", "dw", "db", "ws", "ws_bytes", "split"))
 
 
 def test_the_library_refuses_bad_arguments_before_any_launch():
@@ -64,22 +49,9 @@ def test_the_library_refuses_bad_arguments_before_any_launch():
     shapes = ((dict(Cin=0), "1 to 64"), (dict(Cin=65), "1 to 64"), (dict(Cout=0), "1 to 64"), (dict(Cout=65), "1 to 64"),
               (dict(Cout=-1), "1 to 64"), (dict(B=0), "at least 1"), (dict(B=-3), "at least 1"), (dict(n=0), "at least 1"),
               (dict(n=-2), "at least 1"), (dict(n=1 << 31), "2^31"), (dict(n=1 << 40), "2^31"), (dict(B=1 << 40), "tiles"))
-    for kw, word in shapes:
-        for call in (_fwd, _bwd):
-            assert call(**kw) == INV, (call.__name__, kw)
-            assert word in _lib.last_error(), (call.__name__, kw, _lib.last_error())
-    for call, pointers in ((_fwd, ("x", "w", "y")), (_bwd, ("g", "ws"))):
-        for p in pointers:
-            assert call(**{p: None}) == INV and "NULL" in _lib.last_error(), (call.__name__, p, _lib.last_error())
-    for call, pointers in ((_fwd, ("x", "w", "bias", "y")), (_bwd, ("x", "g", "w", "dx", "dw", "db", "ws"))):
-        for p in pointers:
-            assert call(**{p: FAKE + 8}) == INV and "aligned" in _lib.last_error(), (call.__name__, p, _lib.last_error())
-    # what a gradient needs: w for dx, x for dw and db; and one of the three has to be asked for
-    assert _bwd(w=None) == INV and "NULL" in _lib.last_error()
-    assert _bwd(x=None) == INV and "NULL" in _lib.last_error()
-    assert _bwd(dx=None, dw=None, db=None) == INV and "NULL" in _lib.last_error()
-    for split in (-1, 65):
-        assert _bwd(split=split) == INV and "split" in _lib.last_error()
+    # what a gradient needs beside these: w for dx, x for dw and db; and one of the three has to be asked for
+    cf.check_refusals(_fwd, _bwd, shapes, required=(("x", "w", "y"), ("g", "ws")),
+                      pointers=(("x", "w", "bias", "y"), ("x", "g", "w", "dx", "dw", "db", "ws")))
     need = _lib.lib().mgs_pointwise_workspace_bytes(1, 4, 8, 210)
     assert _bwd(ws_bytes=need - 1) == _lib.MGS_ERR_WORKSPACE and "needed" in _lib.last_error()
     assert _bwd(dw=None, db=None, ws_bytes=need - 1, split=65) == INV, "the split is checked even where dx alone is asked for"
@@ -104,16 +76,7 @@ def test_the_workspace_size_is_zero_for_illegal_shapes_and_follows_the_records_o
 
 
 def test_the_abi_version_is_still_17_and_the_new_names_match_the_ctypes_table():
-    assert _lib.ABI_VERSION == 17 and _lib.lib().mgs_abi_version() == 17
-    hdr = open(os.path.join(ROOT, "include", "mgsplat.h")).read()
-    assert "#define MGS_ABI_VERSION 17" in re.sub(r"[ \t]+", " ", hdr)
-    declared = set(re.findall(r"\b(mgs_[a-z0-9_]+)\s*\(", hdr)) - {"mgs_stream_t"}
-    assert set(_lib.exported_symbols()) == declared
-    for name in NAMES:
-        assert name in declared and hasattr(_lib.lib(), name), name
-        params = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", hdr, re.S).group(1)
-        assert len(params.split(",")) == len(getattr(_lib.lib(), name).argtypes), name
-    assert _lib.lib().mgs_pointwise_workspace_bytes.restype is ctypes.c_size_t
+    cf.check_abi(FAMILY.names)
 
 
 def test_the_op_refuses_cpu_tensors_other_dtypes_and_bad_shapes():
@@ -167,18 +130,8 @@ def test_a_cpu_stem_is_torchs_composition_bit_for_bit_whatever_the_switch(switch
     assert isinstance(m.conv_out, torch.nn.Conv3d) and m.conv_out.bias is not None
 
 
-class _SaidToBeOnDevice(torch.Tensor):
-    """A CPU tensor that answers is_cuda with True: without a GPU the route's other questions can still be asked (its .device stays
-    the host's, which is where the modules' weights then are too)."""
-    is_cuda = property(lambda self: True)
-
-
-def _OnDevice(t):
-    return t.as_subclass(_SaidToBeOnDevice)
-
-
 def test_what_the_route_looks_at(switches):
-    nn = torch.nn
+    nn, _OnDevice = torch.nn, cf.on_device
     m = enc.MultiLayer3DEncoderShallow()
     x = torch.zeros(1, 8, 4, 4, 4)
     switches(pointwise=True)
@@ -218,18 +171,6 @@ def test_what_the_route_looks_at(switches):
     assert not enc._conv_routed(m.conv_out, x, False)
 
 
-def _op_wins(entry):
-    """The criterion of encoder.fused_site(): in all four (pass, form) pairs the op's third quartile lies below the first quartile of
-    torch's faster setting of cudnn.benchmark."""
-    for p in ("forward", "forward_backward"):
-        for f in ("eager", "graph"):
-            sides = entry[p][f]
-            t = min((sides["torch"], sides["torch_benchmark"]), key=lambda s: s["median_us"])
-            if not sides["op"]["q3_us"] < t["q1_us"]:
-                return False
-    return True
-
-
 def test_the_routing_rule_matches_the_committed_measurement():
     """profiles/pointwise_bench.json (scripts/bench_pointwise.py on an MI355X): pointwise_site() routes a shape ONLY where the op won
     all four (pass, form) pairs, and nothing smaller than the smallest measured winner or at channel counts nobody measured."""
@@ -238,7 +179,7 @@ def test_the_routing_rule_matches_the_committed_measurement():
     assert sorted(bench["shapes"]) == sorted(BENCH_SHAPES)
     routed, smallest = [], None
     for name, v in bench["shapes"].items():
-        won = _op_wins(v)
+        won = cf.op_wins(v)
         assert won == v["op_wins"] == bench["routing_as_measured"][name], name
         assert (v["cin"], v["cout"]) == (8, 64) and v["values_per_channel"] == v["side"] ** 3
         rule = enc.pointwise_site(v["cin"], v["cout"], v["values_per_channel"])
@@ -268,144 +209,32 @@ def test_the_switch_follows_the_rule_at_import():
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------------
-def dev():
-    return torch.device("cuda:0")
-
-
-def run(case, split=0, x=None, w=None, b=None, g=None, need=(True, True, True)):
-    """{y, dx, dw, db}: CPU tensors of one forward + backward of the op on the case's inputs (or on x / w / b / g given, on the device)."""
-    t = pc.reference(case)
-    d = dev()
-    x = (t["x"].to(d) if x is None else x).detach().requires_grad_(need[0])
-    w = (t["w"].to(d) if w is None else w).detach().requires_grad_(need[1])
-    if t["b"] is None:
-        b = None
-    else:
-        b = (t["b"].to(d) if b is None else b).detach().requires_grad_(need[2])
-    g = t["g"].to(d) if g is None else g
-    y = pw._pointwise_conv3d(x, w, b, split)
-    if y.requires_grad:
-        y.backward(g)
-    torch.cuda.synchronize()
-
-    def grad(v):
-        return None if v is None or v.grad is None else v.grad.cpu()
-    return {"y": y.detach().cpu(), "dx": grad(x), "dw": grad(w), "db": grad(b)}
+dev = cf.dev
 
 
 @gpu
 @pytest.mark.parametrize("case", pc.ALL)
 def test_every_case_forward_and_all_gradients(case):
-    r = pc.reference(case)
-    got = run(case)
-    fails = []
-    for q in pc.quantities(case):
-        truth, yard = r[q + "64"], r["ref_err"][q]
-        assert yard <= pc.REF_ERR_CEILING, (case, q, yard)
-        assert got[q].shape == truth.shape and got[q].dtype == torch.float32, (case, q, got[q].shape)
-        e, bnd = (got[q].double() - truth).abs().max().item(), pc.bound(yard, truth)
-        print(f"{case} {q}: err {e:.3e}, bound {bnd:.3e} (yardstick {yard:.2e} of {truth.abs().max().item():.3e})")
-        if not e <= bnd:
-            fails.append((q, e, bnd))
-    assert not fails, (case, fails)
-    if not pc.has_bias(case):
-        assert got["db"] is None
+    cf.check_case(FAMILY, case)
 
 
 @gpu
 @pytest.mark.parametrize("case", ["odd", "tail_3", "stem_out_batch", "long_sum", "wide_odd"])
 def test_the_same_bits_across_two_runs_and_across_splits(case):
-    want = run(case)
-    again = run(case)
-    for q in pc.quantities(case):
-        assert pc.same_bits(again[q], want[q]), (case, q, "second run")
-    for split in (1, 2, 7, 64):
-        got = run(case, split=split)
-        for q in pc.quantities(case):
-            assert pc.same_bits(got[q], want[q]), (case, q, split)
-
-
-def _count_calls(monkeypatch):
-    """Replaces the two entry points on the library object by wrappers that record (name, dx, dw, db given) per call."""
-    L = _lib.lib()
-    calls = []
-
-    def wrap(name, real):
-        def f(*a):
-            calls.append((name[len("mgs_pointwise_"):],) + (tuple(bool(p) for p in a[7:10]) if name.endswith("backward") else ()))
-            return real(*a)
-        return f
-    for name in ("mgs_pointwise_forward", "mgs_pointwise_backward"):
-        monkeypatch.setattr(L, name, wrap(name, getattr(L, name)))
-    return calls
+    cf.check_same_bits(FAMILY, case)
 
 
 @gpu
 @pytest.mark.parametrize("case", ["odd", "in_pre", "wide_odd"])
 def test_only_the_requested_gradients_are_computed(case, monkeypatch):
-    calls = _count_calls(monkeypatch)
-    want = run(case)
-    assert calls == [("forward",), ("backward", True, True, True)]
-    del calls[:]
-    only_x = run(case, need=(True, False, False))
-    assert calls == [("forward",), ("backward", True, False, False)], "dx alone: dw and db are passed as null"
-    assert only_x["dw"] is None and only_x["db"] is None and pc.same_bits(only_x["y"], want["y"])
-    # (the input gradient alone is the forward's kernel on the transposed weight, adding in the fused kernel's order)
-    assert pc.same_bits(only_x["dx"], want["dx"])
-    r = pc.reference(case)
-    del calls[:]
-    only_wb = run(case, need=(False, True, True))
-    assert calls == [("forward",), ("backward", False, True, True)]
-    assert only_wb["dx"] is None and pc.same_bits(only_wb["dw"], want["dw"]) and pc.same_bits(only_wb["db"], want["db"])
-    del calls[:]
-    only_b = run(case, need=(False, False, True))
-    assert calls == [("forward",), ("backward", False, False, True)]
-    assert only_b["dx"] is None and only_b["dw"] is None and pc.same_bits(only_b["db"], want["db"])
-    del calls[:]
-    x_and_w = run(case, need=(True, True, False))
-    assert calls == [("forward",), ("backward", True, True, False)]
-    assert x_and_w["db"] is None and pc.same_bits(x_and_w["dx"], want["dx"]) and pc.same_bits(x_and_w["dw"], want["dw"])
-    del calls[:]
-    d = dev()
-    with torch.no_grad():
-        y = pw.pointwise_conv3d(r["x"].to(d), r["w"].to(d), r["b"].to(d))
-    assert calls == [("forward",)] and pc.same_bits(y.cpu(), want["y"])
-    del calls[:]
-    none = run(case, need=(False, False, False))
-    assert calls == [("forward",)] and pc.same_bits(none["y"], want["y"])
+    """dx alone: dw and db are passed as null (and it is the forward's kernel on the transposed weight, adding in the fused kernel's
+    order: the same bits)."""
+    cf.check_requested_gradients(FAMILY, case, monkeypatch)
 
 
 @gpu
 def test_non_contiguous_and_offset_views_give_the_contiguous_result():
-    case = "odd"
-    r = pc.reference(case)
-    want = run(case)
-    d = dev()
-
-    def channels_last(t):
-        v = t.to(d).permute(0, 2, 3, 4, 1).contiguous().permute(0, 4, 1, 2, 3)
-        assert not v.is_contiguous() and torch.equal(v, t.to(d))
-        return v
-
-    def strided(t):   # (a [Cout,Cin,1,1,1] weight and a [Cout] bias have no channels-last form: every other element of a longer vector)
-        v = torch.empty(2 * t.numel(), device=d)[::2].view(t.shape)
-        v.copy_(t)
-        assert not v.is_contiguous() and torch.equal(v, t.to(d))
-        return v
-
-    def shifted(t):
-        flat = torch.empty(t.numel() + 1, device=d)
-        v = flat[1:].view(t.shape)   # contiguous, 4 bytes off a 16-byte boundary
-        v.copy_(t)
-        assert v.is_contiguous() and v.data_ptr() % 16 == 4
-        return v
-
-    for tag, f in (("channels last", channels_last), ("4-byte offset", shifted)):
-        for which in ("x", "w", "b", "g"):
-            view = strided(r[which]) if (which in ("w", "b") and f is channels_last) else f(r[which])
-            got = run(case, **{which: view})
-            for q in pc.quantities(case):
-                assert pc.same_bits(got[q], want[q]), (tag, which, q)
+    cf.check_views(FAMILY, "odd")
 
 
 @gpu
@@ -420,7 +249,7 @@ def test_the_stem_with_conv_out_routed_against_torchs_path(switches, monkeypatch
     gen = torch.Generator().manual_seed(42)
     x = torch.randn(1, 10, 12, 12, 12, generator=gen).to(d)
     g_out, g_v1, g_v2 = (torch.randn(*s, generator=gen).to(d) for s in ((1, 64, 12, 12, 12), (1, 32, 3, 3, 3), (1, 16, 6, 6, 6)))
-    calls = _count_calls(monkeypatch)
+    calls = cf.count_calls(monkeypatch, FAMILY)
 
     def once(pointwise, dtype, where):
         switches(pointwise=pointwise)
@@ -441,15 +270,7 @@ def test_the_stem_with_conv_out_routed_against_torchs_path(switches, monkeypatch
     assert calls == [], "POINTWISE = False: the module's own convolution"
     routed = once(True, torch.float32, d)
     assert calls == [("forward",), ("backward", True, True, True)], calls
-    fails = []
-    for k, want in truth.items():
-        mag = want.abs().max().item()
-        yard = (torchs[k] - want).abs().max().item() / mag
-        e, bnd = (routed[k] - want).abs().max().item(), max(pc.FACTOR * yard, pc.FACTOR * pc.FLOOR) * mag
-        print(f"stem {k}: err {e:.3e}, bound {bnd:.3e} (torch's fp32 path {yard:.2e} of {mag:.3e})")
-        if not e <= bnd:
-            fails.append((k, e, bnd))
-    assert not fails, fails
+    cf.compare_modules("stem", "torch's fp32 path", truth, torchs, routed)
     # the rule leaves a 12^3 volume to torch: the existing small-shape tests run the code they ran before
     del calls[:]
     once(None, torch.float32, d)
@@ -458,10 +279,8 @@ def test_the_stem_with_conv_out_routed_against_torchs_path(switches, monkeypatch
 
 @gpu
 def test_forward_and_backward_captured_into_a_hip_graph():
-    """In a child process: stream capture is process-wide state (tests/tools/pointwise_graph_capture_check.py)."""
-    tool = os.path.join(ROOT, "tests", "tools", "pointwise_graph_capture_check.py")
-    r = subprocess.run(["timeout", "-k", "10", "150", sys.executable, tool], capture_output=True, text=True, timeout=170)
-    assert r.returncode == 0 and "GRAPH_OK" in r.stdout, f"exit {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
+    """In a child process: stream capture is process-wide state (tests/tools/conv_graph_capture_check.py)."""
+    cf.graph_capture(FAMILY.name)
 
 
 @gpu

@@ -1015,6 +1015,43 @@ int mgs_dense_conv3d_backward(int64_t B, int Cin, int Cout, int k, int64_t Di, i
                               const float* x, const float* y, const float* g_y, const float* w, float* dx, float* dw, float* db,
                               float* g_scratch, void* workspace, size_t workspace_bytes, int split, mgs_stream_t stream);
 
+/* ---- the Perceiver's patch embedding: a Conv3d whose stride is its kernel, pad folded in (mgs_patch.hip) ----
+ * patchify = Conv3DBlock(128, 128, kernel_sizes=5, strides=5, activation='relu') on [B,128,100^3] with replicate pad 2.  k is the
+ * kernel AND the stride, cubic, 2..5; pad 0..k-1 on every side, zeros_pad 0: replicate (a clamp), 1: zeros (a mask); dilation 1, groups
+ * 1; Cin a multiple of 8 in 8..256, Cout a multiple of 32 in 32..256.  Do = (Di + 2 pad - k) / k + 1, and so Ho, Wo; the input
+ * coordinate of (output o, tap t) is i = o k + t - pad.  x and dx [B, Cin, Di, Hi, Wi], y and g_y [B, Cout, Do, Ho, Wo], w and dw
+ * [Cout, Cin, k, k, k], bias and db [Cout]: all contiguous and 16-byte aligned.  negative_slope < 0: no activation; >= 0:
+ * act(z) = z > 0 ? z : negative_slope z (0: ReLU).  The padded volume is never written.
+ *   forward:   y[b,co,o]     = act(bias[co] + sum_ci sum_t w[co,ci,t] x[b,ci,i(o,t)])                      (bias may be NULL: no bias)
+ *   backward:  g'            = g_y (y > 0 ? 1 : negative_slope), or g_y without an activation (y may then be NULL)
+ *              dx[b,ci,i]    = sum over the (o,t) that map onto i, sum_co w[co,ci,t] g'[b,co,o]: one (o,t) in the interior, up to
+ *                              (pad + 1)^3 taps on a replicate border, added in ascending tap order; a voxel past the last patch
+ *                              belongs to no output and its dx is ZERO, written by the call itself (dx needs no zeroing)
+ *              dw[co,ci,t]   = sum_b sum_o g'[b,co,o] x[b,ci,i(o,t)];   db[co] = sum_b sum_o g'[b,co,o]
+ * All products run on v_mfma_f32_32x32x2_f32: k-ordered chains of fused multiply-adds in fp32, over tiles of 32 patches consecutive
+ * in (od, oh, ow) order.  The forward is two launches: the weights are rearranged into the workspace in the order the k loop consumes
+ * them, then one GEMM whose K dimension is not split.  dx, dw and db may each be NULL and only what is asked for is computed.  dx is
+ * one launch and needs no workspace.  dw and db are two launches: the tiles of 32 patches, in their linear order, are cut into runs
+ * whose number (at most 64; as many as fit 64 MB, at least 2) and length depend on the shape alone, every run is summed to one RECORD
+ * [Cout, Cin k^3 + 1] in the workspace (db, the last column, in double), and the second launch adds the records in ascending order, in
+ * double.  split (0: chosen from the shape; 1..64: forced, a test aid; never more than the number of runs) is the number of
+ * workgroups that share the runs: it says which workgroup computes a record, never what the record is.
+ * workspace: 16-byte aligned, at least as many bytes as the size query returns for the same shape (0 for shapes outside the limits,
+ * else a multiple of 256); needed by the forward, and by the backward where dw or db is asked for (else it may be NULL).
+ * MGS_ERR_INVALID_ARG before any launch: k outside 2..5; pad outside 0..k-1; Cin or Cout outside their limits or off their
+ * multiples; B below 1 or above 65535; an extent below 1 or, padded, below k; Di Hi Wi >= 2^31; B Do Ho Wo >= 2^31; zeros_pad other
+ * than 0 or 1; a NaN slope; a NULL pointer where one is required (dx, dw and db all NULL included); a pointer not 16-byte aligned;
+ * split outside [0, 64].  MGS_ERR_WORKSPACE: fewer bytes than the query's.  Element offsets are 64-bit.
+ * No atomics, no workgroup waits for another, nothing to zero: bit-identical from run to run; dx is the same bits whether or not dw
+ * and db are asked for.  No host read, no allocation, no state: capturable into a HIP graph. */
+size_t mgs_patch_conv3d_workspace_bytes(int64_t B, int Cin, int Cout, int k, int pad, int64_t Di, int64_t Hi, int64_t Wi);
+int mgs_patch_conv3d_forward(int64_t B, int Cin, int Cout, int k, int pad, int64_t Di, int64_t Hi, int64_t Wi, int zeros_pad,
+                             float negative_slope, const float* x, const float* w, const float* bias, float* y, void* workspace,
+                             size_t workspace_bytes, mgs_stream_t stream);
+int mgs_patch_conv3d_backward(int64_t B, int Cin, int Cout, int k, int pad, int64_t Di, int64_t Hi, int64_t Wi, int zeros_pad,
+                              float negative_slope, const float* x, const float* y, const float* g_y, const float* w, float* dx,
+                              float* dw, float* db, void* workspace, size_t workspace_bytes, int split, mgs_stream_t stream);
+
 /* Per-stage device timing (hipEvents on the caller's stream), enabled with
  * mgs_set_option("profile", 1) (render backward only) or 2 (every stage).  mgs_profile_read waits for the
  * recorded events, writes the summed milliseconds and launch counts per stage ([mgs_profile_num_stages()]),

@@ -21,6 +21,7 @@ from .conv3d import conv3d, conv_transpose3d  # noqa: F401
 from .pointwise import pointwise_conv3d  # noqa: F401
 from .narrow import narrow_conv3d  # noqa: F401
 from .dense import dense_conv3d  # noqa: F401
+from .patch import patch_conv3d  # noqa: F401
 from .augmentation import (Se3Augmentation, apply_se3_augmentation,  # noqa: F401
                            apply_se3_augmentation_with_camera_pose)
 from . import camera  # noqa: F401

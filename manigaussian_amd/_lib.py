@@ -280,6 +280,11 @@ _EXPORTS = {
                                  [ctypes.c_float] + [c_fp] * 5 + [c_sz, c_fp]),
     "mgs_dense_conv3d_backward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_int64] * 3 +
                                   [ctypes.c_float] + [c_fp] * 9 + [c_sz, ctypes.c_int, c_fp]),
+    "mgs_patch_conv3d_workspace_bytes": (c_sz, [ctypes.c_int64] + [ctypes.c_int] * 4 + [ctypes.c_int64] * 3),
+    "mgs_patch_conv3d_forward": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int] * 4 + [ctypes.c_int64] * 3 +
+                                 [ctypes.c_int, ctypes.c_float] + [c_fp] * 5 + [c_sz, c_fp]),
+    "mgs_patch_conv3d_backward": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int] * 4 + [ctypes.c_int64] * 3 +
+                                  [ctypes.c_int, ctypes.c_float] + [c_fp] * 8 + [c_sz, ctypes.c_int, c_fp]),
     "mgs_forward_stats": (ctypes.c_int, [ctypes.POINTER(MgsRasterArgs), c_i32, ctypes.POINTER(ctypes.c_int64),
                                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), c_fp]),
     "mgs_debug_geom_layout": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(c_sz)] * 4),

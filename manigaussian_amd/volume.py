@@ -16,7 +16,9 @@ The one exception is a 3x3x3 block with at most 4 output channels (trans_decoder
 says so (NARROW overrides it) it goes through narrow_conv3d (narrow.py, csrc/mgs_narrow.hip), which folds the pad into its
 addressing, so that the input is not padded first.  A dense 3x3x3 or 5x5x5 block at channel counts dense_conv3d takes (up0's two
 blocks and final) runs its convolution, bias and ReLU / leaky ReLU as one op on the volume this module padded (dense.py,
-csrc/mgs_dense.hip) where dense_site() says so (DENSE overrides it).
+csrc/mgs_dense.hip) where dense_site() says so (DENSE overrides it).  A block whose stride is its kernel (the Perceiver's patchify,
+perceiver_lang_io.py:235) goes through patch_conv3d (patch.py, csrc/mgs_patch.hip) -- pad, convolution, bias and activation in one op on
+the unpadded volume -- where patch_site() says so (PATCH overrides it).
 """
 import ctypes
 
@@ -26,6 +28,7 @@ from torch import nn
 
 from . import _conv, _lib, _ops
 from . import dense as _dense
+from . import patch as _patch
 from .dense import dense_conv3d
 from .narrow import MAX_CIN as NARROW_MAX_CIN, MAX_COUT as NARROW_MAX_COUT, narrow_conv3d
 
@@ -104,6 +107,41 @@ def _dense_routed(conv, x):
     if DENSE:
         return True
     return dense_site(conv.in_channels, conv.out_channels, k[0], (x.size(2) - k[0] + 1) * (x.size(3) - k[0] + 1) * (x.size(4) - k[0] + 1))
+
+
+# Whether a block whose stride is its kernel goes through patch_conv3d (csrc/mgs_patch.hip).  PATCH: None = follow patch_site();
+# True / False = every eligible block / none (tests, scripts/bench_patch.py).
+PATCH = None
+# (cin, cout, k) -> input voxels D H W of the smallest measured winner at these channel counts (scripts/bench_patch.py ->
+# profiles/patch_conv_bench.json); a triple that was not measured, or that won nowhere, is not here
+PATCH_MIN_VOXELS = {}
+
+
+def patch_site(cin, cout, k, voxels):
+    """The routing rule of the kernel = stride blocks (voxels = input D H W), from the measurement (scripts/bench_patch.py ->
+    profiles/patch_conv_bench.json), by encoder.fused_site()'s criterion: a shape is routed only where the op's third
+    quartile lay below the first quartile of the parent's path (resample_pad + F.conv3d(stride=k) + the activation, at the faster of
+    cudnn.benchmark off and on) for forward AND forward + backward, eager AND graph-replayed.  Only measured (cin, cout, k) triples
+    are routed, each from its smallest measured winner's size up."""
+    least = PATCH_MIN_VOXELS.get((cin, cout, k))
+    return least is not None and voxels >= least
+
+
+def _patch_routed(conv, x, activation=None):
+    """Whether `conv` (an nn.Conv3d whose stride is its cubic kernel) followed by `activation` goes through the kernels on x, the
+    volume WITHOUT its padding."""
+    if PATCH is False or not _conv.routable(x, conv.weight, conv.bias):
+        return False
+    k, p = conv.kernel_size, conv.padding
+    if len(set(k)) != 1 or conv.stride != k or conv.dilation != (1, 1, 1) or conv.groups != 1 or x.size(1) != conv.in_channels:
+        return False
+    if conv.padding_mode not in _patch.PADDING_MODES or isinstance(p, str) or len(set(p)) != 1:
+        return False
+    if not _patch.eligible(conv.in_channels, conv.out_channels, k[0], p[0], tuple(x.shape[2:]), x.size(0)):
+        return False
+    if not _dense_slope(activation)[0]:
+        return False
+    return True if PATCH else patch_site(conv.in_channels, conv.out_channels, k[0], x[0, 0].numel())
 
 
 def _in_place(t):
@@ -252,6 +290,9 @@ class Conv3DBlock(nn.Module):
             c = self.conv3d
             x = narrow_conv3d(x, c.weight, c.bias, c.padding_mode)
             return self.activation(x) if self.activation is not None else x
+        if not several and _patch_routed(self.conv3d, x, self.activation):
+            c = self.conv3d
+            return _patch.patch_conv3d(x, c.weight, c.bias, c.padding[0], c.padding_mode, _dense_slope(self.activation)[1])
         pad = self.fused_pad()
         if pad == 0 and not several and _dense_routed(self.conv3d, x):
             return self.forward_padded(x)

@@ -70,8 +70,10 @@ def workspace(dev, nbytes):
     """The device's scratch tensor of nbytes bytes (uint8), one per (device index, bytes), allocated on first use.
 
     The contract every op that takes one relies on: its contents are undefined between calls; an op writes what it reads
-    within the same call.  The tensor is shared by all streams of the device, so two streams running the same op concurrently
-    on one device are not supported.  It is never freed, so its address stays valid for captured graphs."""
+    within the same call (tests/test_poisoned_memory.py holds every op to it: it fills the workspace with 0xFF and with 0x7F
+    bytes at every fetch and asks for the bits of the clean run).  The tensor is shared by all streams of the device, so two
+    streams running the same op concurrently on one device are not supported.  It is never freed, so its address stays valid
+    for captured graphs."""
     key = (_index(dev), nbytes)
     ws = _WORKSPACES.get(key)
     if ws is None:

@@ -6,7 +6,8 @@
 // workgroups that share the runs: it decides who computes a record, not what the record is.  The merge launch then sums the records
 // in ascending order in double and rounds once: dw and db are the same bits for every split.  A record is written before it is read
 // within one call (the merge follows the family's kernel on the same stream), so the workspace needs no zeroing and carries nothing
-// from one call to the next.
+// from one call to the next.  tests/test_poisoned_memory.py holds the families to that: every split and every combination of requested
+// gradients with the workspace and the results filled with 0xFF and with 0x7F bytes beforehand, against the bits of the clean run.
 #include "mgs_common.h"
 
 namespace mgs {

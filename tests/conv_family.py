@@ -1,5 +1,5 @@
-"""The harness of the four Conv3d families' tests (tests/test_conv3d.py, test_pointwise.py, test_narrow_conv.py, test_dense_conv.py)
-and of their graph tool (tests/tools/conv_graph_capture_check.py) -- TEST INFRASTRUCTURE, not a test file.
+"""The harness of the Conv3d families' tests (tests/test_conv3d.py, test_pointwise.py, test_narrow_conv.py, test_dense_conv.py,
+test_patch_conv.py, and test_poisoned_memory.py, which walks all five) and of their graph tool (tests/tools/conv_graph_capture_check.py) -- TEST INFRASTRUCTURE, not a test file.
 
 A family is a Family record in FAMILIES: its cases module, its C entry points, how a case's extra arguments reach its op, and what
 its backward is handed beside dx, dw and db.  Over that record this file holds once what every family's tests do: one forward +
@@ -18,6 +18,7 @@ import torch
 import conv3d_cases
 import dense_conv_cases
 import narrow_conv_cases
+import patch_conv_cases
 import pointwise_cases
 from conv_cases import FACTOR, FLOOR, same_bits
 from manigaussian_amd import _lib
@@ -94,6 +95,9 @@ FAMILIES = {f.name: f for f in (
     # the padded gradient is allocated where dx is asked for
     Family("dense", dense_conv_cases, "mgs_dense_conv3d_", _dense, ("odd_k3", "up0_last_head"), splits=(1, 3, 64),
            watched=("dx", "dw", "db", "g_scratch"), also_given=lambda need: (need[0],)),
+    # the workspace is passed where dw or db is asked for (its graph tool is its own: tests/tools/patch_graph_capture_check.py)
+    Family("patch", patch_conv_cases, "mgs_patch_conv3d_", patch_conv_cases.call, ("odd", "site_small"), splits=(1, 3, 64),
+           watched=("dx", "dw", "db", "workspace"), also_given=lambda need: (need[1] or need[2],)),
 )}
 
 

@@ -25,10 +25,8 @@ pt = importlib.import_module("manigaussian_amd.patch")
 gpu = pytest.mark.gpu
 ROOT = cf.ROOT
 GRAPH_TOOL = os.path.join(ROOT, "tests", "tools", "patch_graph_capture_check.py")
-GRAPH_CASES = ("odd", "site_small")
-# the workspace is passed where dw or db is asked for
-FAMILY = cf.Family("patch", pc, "mgs_patch_conv3d_", pc.call, GRAPH_CASES, splits=(1, 3, 64), watched=("dx", "dw", "db", "workspace"),
-                   also_given=lambda need: (need[1] or need[2],))
+FAMILY = cf.FAMILIES["patch"]   # (the workspace is passed where dw or db is asked for)
+GRAPH_CASES = FAMILY.graph_cases
 BENCH_SHAPES = {"patchify_100": (128, 128, 100), "patchify_50": (128, 128, 50), "patchify_25": (128, 128, 25), "peract_100": (64, 64, 100)}
 
 

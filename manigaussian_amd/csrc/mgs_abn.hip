@@ -229,12 +229,27 @@ __global__ __launch_bounds__(ABN_THREADS) void abn_apply_kernel(AbnGeom g, AbnFw
     const double n = (double)g.B * (double)g.N;
     mean = (float)dmean;
     invstd = (float)(1.0 / sqrt(dm2 / n + (double)a.eps));
+    double rmean = dmean;
+    if (b == 0 && slice == 0 && a.running_mean && dmean != dmean) {   // (uniform across the workgroup, and rare)
+      // A merged mean is NaN for a channel that holds an infinity (inf - inf between two parts) where the plain mean the reference
+      // takes is that infinity.  Everything computed FROM the mean is NaN either way; the running mean is not.  The workgroup looks.
+      int seen = 0;
+      for (uint32_t bb = 0; bb < g.B; ++bb) {
+        const float* xc = a.x + ((int64_t)bb * g.C + c) * (int64_t)g.N;
+        for (uint32_t i = tid; i < g.N; i += ABN_THREADS) {
+          const float v = xc[i];
+          seen |= v != v ? 4 : (v == INFINITY ? 1 : (v == -INFINITY ? 2 : 0));
+        }
+      }
+      const int pos = __syncthreads_or(seen & 1), neg = __syncthreads_or(seen & 2), nan = __syncthreads_or(seen & 4);
+      if (!nan && (pos != 0) != (neg != 0)) rmean = pos ? (double)INFINITY : -(double)INFINITY;
+    }
     if (b == 0 && slice == 0 && tid == 0) {   // once per channel
       a.stats[2 * c] = mean;
       a.stats[2 * c + 1] = invstd;
       if (a.running_mean) {
         const double m = (double)a.momentum;
-        a.running_mean[c] = (float)((1.0 - m) * (double)a.running_mean[c] + m * dmean);
+        a.running_mean[c] = (float)((1.0 - m) * (double)a.running_mean[c] + m * rmean);
         a.running_var[c] = (float)((1.0 - m) * (double)a.running_var[c] + m * (dm2 / (n - 1.0)));
       }
       if (a.num_batches_tracked && c == 0) a.num_batches_tracked[0] += 1;

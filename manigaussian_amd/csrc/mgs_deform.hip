@@ -59,7 +59,8 @@ __global__ void __launch_bounds__(256) deform_apply_fwd_kernel(int N, const floa
   float q[4], n2 = 0.f;
 #pragma unroll
   for (int c = 0; c < 4; c++) { q[c] = rot[4 * (size_t)n + c] + d[3 + c]; n2 += q[c] * q[c]; }
-  const float inv = 1.0f / fmaxf(sqrtf(n2), 1e-12f);  // F.normalize eps
+  const float nn = sqrtf(n2);
+  const float inv = 1.0f / (nn < 1e-12f ? 1e-12f : nn);  // F.normalize eps; a comparison: a NaN norm stays NaN (fmaxf drops it)
 #pragma unroll
   for (int c = 0; c < 4; c++) rot_out[4 * (size_t)n + c] = q[c] * inv;
 }
@@ -84,7 +85,7 @@ __global__ void __launch_bounds__(256) deform_apply_bwd_kernel(int N, const floa
     dt += q[c] * g[c];
   }
   const float nn = sqrtf(n2);
-  if (nn > 1e-12f) {
+  if (!(nn <= 1e-12f)) {  // (a NaN norm takes the general branch and stays NaN)
     const float inv = 1.0f / nn, inv3 = inv * inv * inv;
 #pragma unroll
     for (int c = 0; c < 4; c++) o[3 + c] = g[c] * inv - q[c] * dt * inv3;

@@ -83,7 +83,44 @@ __global__ __launch_bounds__(DC_THREADS) void dc_prep_kernel(int K3, int CinG, i
   const int st = row >> 3, j = row & 7, cs = st / K3, tap = st - cs * K3, ci = cs * DC_KS + j;
   float v = 0.f;
   if (co < CoutG) v = flipped ? w[((int64_t)ci * CoutG + co) * K3 + (K3 - 1 - tap)] : w[((int64_t)co * CinG + ci) * K3 + tap];
+  // Backward-data multiplies every weight by the zero padding of g': a NaN or infinite weight would put a NaN into every dx the
+  // padding connects it to.  It goes into the GEMM as a zero, and dc_dx_nonfinite_kernel adds what it does contribute.
+  if (flipped && !(fabsf(v) < INFINITY)) v = 0.f;
   wp[e] = v;
+}
+
+// dx += w[co][ci][tap] g'[b][co][i - tap] for the weights that are NaN or infinite, over the voxels i whose i - tap is an output voxel.
+// grid = (Cin, B): a workgroup looks through its input channel's Cout k^3 weights and leaves if all are finite (every training step).
+// int indices: dc_shape admits rows of fewer than 2^31 elements (vin, and Cout k^3 <= 256 x 125); offsets across rows are 64-bit.
+__global__ __launch_bounds__(DC_THREADS) void dc_dx_nonfinite_kernel(int K, int Cin, int Cout, int Di, int Hi, int Wi, int act, float slope,
+                                                                     const float* __restrict__ w, const float* __restrict__ gy,
+                                                                     const float* __restrict__ y, float* __restrict__ dx) {
+  const int ci = (int)blockIdx.x, b = (int)blockIdx.y, K3 = K * K * K, n = Cout * K3;
+  int any = 0;
+  for (int e = (int)threadIdx.x; e < n; e += DC_THREADS) {
+    const int co = e / K3, tap = e - co * K3;
+    any |= !(fabsf(w[((int64_t)co * Cin + ci) * K3 + tap]) < INFINITY);
+  }
+  if (!__syncthreads_or(any)) return;
+  const int Do = Di - K + 1, Ho = Hi - K + 1, Wo = Wi - K + 1, vin = Di * Hi * Wi;
+  const int64_t vout = (int64_t)Do * Ho * Wo;
+  float* dr = dx + ((int64_t)b * Cin + ci) * vin;
+  for (int e = 0; e < n; ++e) {   // (uniform; a thread owns the same voxels for every weight: no two threads add to one element)
+    const int co = e / K3, tap = e - co * K3;
+    const float wv = w[((int64_t)co * Cin + ci) * K3 + tap];
+    if (fabsf(wv) < INFINITY) continue;
+    const int kd = tap / (K * K), r = tap - kd * (K * K), kh = r / K, kw = r - kh * K;
+    const int64_t row = ((int64_t)b * Cout + co) * vout;
+    for (int i = (int)threadIdx.x; i < vin; i += DC_THREADS) {
+      const int d = i / (Hi * Wi), r2 = i - d * (Hi * Wi), h = r2 / Wi, c = r2 - h * Wi;
+      const int od = d - kd, oh = h - kh, ow = c - kw;
+      if ((unsigned)od >= (unsigned)Do || (unsigned)oh >= (unsigned)Ho || (unsigned)ow >= (unsigned)Wo) continue;
+      const int64_t idx = row + ((int64_t)od * Ho + oh) * Wo + ow;
+      float gv = gy[idx];
+      if (act) gv = y[idx] > 0.f ? gv : gv * slope;
+      dr[i] += wv * gv;
+    }
+  }
 }
 
 // ---- forward (and backward-data) ---------------------------------------------------------------------------------------------------
@@ -300,11 +337,13 @@ __global__ __launch_bounds__(DC_THREADS, 2) void dc_bwd_weight_kernel(DcWGeom g,
         bsum += s;
       }
       if (g.want_dw) {
-        const int ks = (nv + 1) >> 1;   // (an odd segment's last step multiplies a zero of g')
+        const int ks = (nv + 1) >> 1;   // (an odd segment's last step multiplies a zero of g' ...)
         for (int k = 0; k < ks; ++k) {
           const int v = 2 * k + kh;
           const float a0 = gs[aoff + v], a1 = gs[aoff + 32 * DC_GROW + v];
-          const float b0 = xs[xoff[0] + v], b1 = xs[xoff[1] + v];
+          // (... by a zero, not by the next voxel's x: 0 x NaN or 0 x inf would put a NaN into sums that voxel has no part in)
+          const bool there = v < nv;
+          const float b0 = there ? xs[xoff[0] + v] : 0.f, b1 = there ? xs[xoff[1] + v] : 0.f;
           if (live[0]) {
             acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
             acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
@@ -471,6 +510,8 @@ int mgs_dense_conv3d_backward(int64_t B, int Cin, int Cout, int k, int64_t Di, i
                        g_y, y, g_scratch);
     dc_launch_prep(sh.K3, Cout, Cin, 1, w, wp, s);
     dc_launch_gemm(k, B, Cout, Cin, Di + P, Hi + P, Wi + P, 0, 0.f, g_scratch, wp, nullptr, dx, s);
+    hipLaunchKernelGGL(dc_dx_nonfinite_kernel, dim3((unsigned)Cin, (unsigned)B), dim3(DC_THREADS), 0, s, k, Cin, Cout, (int)Di, (int)Hi,
+                       (int)Wi, act, negative_slope, w, g_y, y, dx);
   }
   if (dw || db) {
     DcWGeom g;

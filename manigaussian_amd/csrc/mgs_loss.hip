@@ -163,6 +163,10 @@ __device__ __forceinline__ float l2_pass(const LossTarget& t, const float* __res
   return s;
 }
 
+// torch's min() and max() are NaN for a tensor that holds one; fminf and fmaxf drop it
+__device__ __forceinline__ float loss_min(float a, float b) { return __builtin_isunordered(a, b) ? __builtin_nanf("") : fminf(a, b); }
+__device__ __forceinline__ float loss_max(float a, float b) { return __builtin_isunordered(a, b) ? __builtin_nanf("") : fmaxf(a, b); }
+
 __global__ void __launch_bounds__(LOSS_WG) render_loss_minmax_kernel(LossTarget t, int F, int W, int N, float* mm) {
   const int v = blockIdx.y;
   const float* base = t.p + (size_t)v * t.sv;
@@ -172,14 +176,14 @@ __global__ void __launch_bounds__(LOSS_WG) render_loss_minmax_kernel(LossTarget 
     const float* px = base + y * t.sh + x * t.sw;
     for (int c = 0; c < F; c++) {
       const float g = px[c * t.sc];
-      lo = fminf(lo, g);
-      hi = fmaxf(hi, g);
+      lo = loss_min(lo, g);
+      hi = loss_max(hi, g);
     }
   }
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) {
-    lo = fminf(lo, __shfl_xor(lo, d, 64));
-    hi = fmaxf(hi, __shfl_xor(hi, d, 64));
+    lo = loss_min(lo, __shfl_xor(lo, d, 64));
+    hi = loss_max(hi, __shfl_xor(hi, d, 64));
   }
   __shared__ float s[LOSS_WG / WAVE][2];
   const int wave = threadIdx.x / WAVE;
@@ -187,8 +191,8 @@ __global__ void __launch_bounds__(LOSS_WG) render_loss_minmax_kernel(LossTarget 
   __syncthreads();
   if (threadIdx.x == 0) {
     float* o = mm + 2 * ((size_t)v * LOSS_MM + blockIdx.x);
-    o[0] = fminf(fminf(s[0][0], s[1][0]), fminf(s[2][0], s[3][0]));
-    o[1] = fmaxf(fmaxf(s[0][1], s[1][1]), fmaxf(s[2][1], s[3][1]));
+    o[0] = loss_min(loss_min(s[0][0], s[1][0]), loss_min(s[2][0], s[3][0]));
+    o[1] = loss_max(loss_max(s[0][1], s[1][1]), loss_max(s[2][1], s[3][1]));
   }
 }
 
@@ -208,8 +212,8 @@ __global__ void __launch_bounds__(LOSS_WG) render_loss_fwd_kernel(LossArgs a) {
       float lo = a.mm[2 * ((size_t)v * LOSS_MM + threadIdx.x)], hi = a.mm[2 * ((size_t)v * LOSS_MM + threadIdx.x) + 1];
 #pragma unroll
       for (int d = 32; d >= 1; d >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, d, 64));
-        hi = fmaxf(hi, __shfl_xor(hi, d, 64));
+        lo = loss_min(lo, __shfl_xor(lo, d, 64));
+        hi = loss_max(hi, __shfl_xor(hi, d, 64));
       }
       if (threadIdx.x == 0) { s_mm[0] = lo; s_mm[1] = hi; }
     }
@@ -269,11 +273,12 @@ __global__ void __launch_bounds__(LOSS_WG) render_loss_fwd_kernel(LossArgs a) {
 #pragma unroll
         for (int j = 0; j < LOSS_PX; j++) {
           const float n = sqrtf(nn[j]), m = sqrtf(mm[j]);
-          const float n_c = fmaxf(n, COS_EPS), m_c = fmaxf(m, COS_EPS);
+          // clamp_min as comparisons: a NaN norm stays NaN, as in ATen (fmaxf would make it eps)
+          const float n_c = n < COS_EPS ? COS_EPS : n, m_c = m < COS_EPS ? COS_EPS : m;
           const float cs = dot[j] / (n_c * m_c);
           s_emb += cs;  // (a pixel past the image: e = g = 0, cs = 0)
           ka[j] = kn / (n_c * m_c);
-          kb[j] = n > 0.f ? -kn * cs / (n_c * n) : 0.f;
+          kb[j] = !(n <= 0.f) ? -kn * cs / (n_c * n) : 0.f;   // (a NaN norm takes the general branch)
         }
         if (gb) {  // second pass over the channels (L2 hits) instead of 2 x 4 x F values in registers
           for (c = 0; c + 4 <= F; c += 4)

@@ -3,7 +3,7 @@
 // autograd's ReLU / residual / bias / bias-gradient passes were 4 ms of a 22 ms configs[3] step.  Streaming kernels, HBM-bound.
 //   forward :  a = relu(x),  xb = x + bias          one read, two writes (the residual stream picks up the biases that are
 //                                                   added to it later, so that the next GEMM can accumulate into it)
-//   backward:  g = g_pre * (act > 0) [+ g_res],  colsum[n] += sum_m g[m][n]     (ReLU mask, residual add and the bias
+//   backward:  g = (act <= 0 ? 0 : g_pre) [+ g_res],  colsum[n] += sum_m g[m][n]     (ReLU mask, residual add and the bias
 //                                                   gradient in one pass instead of three)
 #include "mgs_common.h"
 
@@ -14,7 +14,8 @@ __global__ void __launch_bounds__(256) mlp_relu_bias_kernel(size_t total4, int n
                                                             float4* __restrict__ xb) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (size_t)gridDim.x * blockDim.x) {
     const float4 v = x[i];
-    if (a) a[i] = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
+    // selects, not fmaxf: a NaN stays a NaN as in torch.relu (fmaxf drops it); -0 still becomes +0
+    if (a) a[i] = make_float4(v.x <= 0.f ? 0.f : v.x, v.y <= 0.f ? 0.f : v.y, v.z <= 0.f ? 0.f : v.z, v.w <= 0.f ? 0.f : v.w);
     if (xb) {
       float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
       if (bias) b = bias[i % (size_t)n4];
@@ -52,8 +53,9 @@ __global__ void __launch_bounds__(256) mlp_relu_bwd_kernel(int M, int n4, const 
     for (int u = 0; u < U; u++) {
       const int r = rb + u * rstep;
       if (r >= row_end) break;
-      float4 g = make_float4(av[u].x > 0.f ? gp[u].x : 0.f, av[u].y > 0.f ? gp[u].y : 0.f, av[u].z > 0.f ? gp[u].z : 0.f,
-                             av[u].w > 0.f ? gp[u].w : 0.f);
+      // act <= 0 ? 0 : g (torch's threshold_backward): the gradient of a NaN unit passes
+      float4 g = make_float4(av[u].x <= 0.f ? 0.f : gp[u].x, av[u].y <= 0.f ? 0.f : gp[u].y, av[u].z <= 0.f ? 0.f : gp[u].z,
+                             av[u].w <= 0.f ? 0.f : gp[u].w);
       g.x += q[u].x; g.y += q[u].y; g.z += q[u].z; g.w += q[u].w;
       g_out[(size_t)r * n4 + c4] = g;
       s.x += g.x; s.y += g.y; s.z += g.z; s.w += g.w;

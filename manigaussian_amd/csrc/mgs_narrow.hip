@@ -351,6 +351,38 @@ __device__ __forceinline__ float nc_wave_sum(float v) {   // the 64 lanes' value
 template <int CO>
 struct NcBw { static constexpr int CIG = CO == 1 ? 2 : 1; };
 
+// One channel's halo box against the thread's 4 (D) x 4 (W) voxels: acc[co][tap] += g[co][voxel] x[voxel + tap].  A voxel outside the
+// volume takes no part: its g is a zero, but its taps are clamped copies of border voxels, and 0 x NaN or 0 x inf would put a NaN
+// into sums the voxel has nothing to do with.  Along D the voxels that exist are the first ndz (uniform across the wave: a skipped
+// plane), along W the first nw; EDGE: nw < 4, the thread straddles the volume's end (W no multiple of 4 only) and the taps of its
+// missing voxels are selected zeros.  A thread with no voxel at all does not come here.
+template <int CO, bool EDGE>
+__device__ __forceinline__ void nc_dw_planes(float (&acc)[CO][NC_TAPS], const float (&gv)[CO][4][4], const float* tp, int ndz, int nw) {
+#pragma unroll
+  for (int q = 0; q < 6; ++q) {
+    float xv[3][6];
+    nc_plane_fence();
+    nc_rows(xv, tp + q * NC_PLANE);
+#pragma unroll
+    for (int kd = 0; kd < 3; ++kd) {
+      const int dz = q - kd;
+      if (dz < 0 || dz > 3) continue;
+      if (dz >= ndz) continue;
+#pragma unroll
+      for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw)
+#pragma unroll
+          for (int wx = 0; wx < 4; ++wx) {
+            const float xx = (EDGE && wx >= nw) ? 0.f : xv[kh][wx + kw];
+#pragma unroll
+            for (int co = 0; co < CO; ++co)
+              acc[co][kd * 9 + kh * 3 + kw] = fmaf(gv[co][dz][wx], xx, acc[co][kd * 9 + kh * 3 + kw]);
+          }
+    }
+  }
+}
+
 // grid = (workgroups per group of input channels, ceil(Cin / CIG) -- or 1 when dw is not wanted: then x is not read)
 template <int CO>
 __global__ __launch_bounds__(NC_GROUP, 2) void nc_bwd_weight_kernel(NcGeom g, uint32_t nrec, uint32_t tpr, uint32_t ntiles, int want_dw,
@@ -398,6 +430,8 @@ __global__ __launch_bounds__(NC_GROUP, 2) void nc_bwd_weight_kernel(NcGeom g, ui
           }
         }
       if (!want_dw) continue;   // (uniform across the launch)
+      const int nw = oh < g.H ? g.W - ow : 0;                                          // the thread's voxels along W that exist (<= 0: none)
+      const int ndz = __builtin_amdgcn_readfirstlane(g.D - (p.d0 + 4 * tz));          // ... along D: tz is the wave
       float v[NC_PER];
       __syncthreads();   // (the last tile's offsets are no longer read)
       int ts = t;   // (opaque: or the 27 elements' box coordinates are kept across the tiles, 81 registers)
@@ -411,27 +445,9 @@ __global__ __launch_bounds__(NC_GROUP, 2) void nc_bwd_weight_kernel(NcGeom g, ui
         if (j < nci) nc_put(box, v, none, t);
         __syncthreads();
         if (j + 1 < nci) nc_fetch(v, xb + (int64_t)(j + 1) * g.vol, tab, t);   // in flight while this channel is used
-        if (j < nci) {
-#pragma unroll
-          for (int q = 0; q < 6; ++q) {
-            float xv[3][6];
-            nc_plane_fence();
-            nc_rows(xv, tp + q * NC_PLANE);
-#pragma unroll
-            for (int kd = 0; kd < 3; ++kd) {
-              const int dz = q - kd;
-              if (dz < 0 || dz > 3) continue;
-#pragma unroll
-              for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-                for (int kw = 0; kw < 3; ++kw)
-#pragma unroll
-                  for (int wx = 0; wx < 4; ++wx)
-#pragma unroll
-                    for (int co = 0; co < CO; ++co)
-                      acc[j][co][kd * 9 + kh * 3 + kw] = fmaf(gv[co][dz][wx], xv[kh][wx + kw], acc[j][co][kd * 9 + kh * 3 + kw]);
-            }
-          }
+        if (j < nci && nw > 0) {
+          if (nw >= 4) nc_dw_planes<CO, false>(acc[j], gv, tp, ndz, 4);
+          else nc_dw_planes<CO, true>(acc[j], gv, tp, ndz, nw);
         }
       }
     }

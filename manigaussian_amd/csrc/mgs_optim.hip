@@ -135,7 +135,8 @@ __global__ void __launch_bounds__(LAMB_WG) lamb_apply_kernel(LambArgs a) {
   __syncthreads();
   sp = (s_part[0][0] + s_part[1][0]) + (s_part[2][0] + s_part[3][0]);
   su = (s_part[0][1] + s_part[1][1]) + (s_part[2][1] + s_part[3][1]);
-  const float weight_norm = fminf((float)sqrt(sp), 10.0f);  // clamp(0, 10), lamb.py:92
+  const float wn = (float)sqrt(sp);
+  const float weight_norm = wn > 10.0f ? 10.0f : wn;  // clamp(0, 10), lamb.py:92; a comparison: a NaN norm stays NaN (fminf drops it)
   const float adam_norm = (float)sqrt(su);
   const float trust = (weight_norm == 0.f || adam_norm == 0.f) ? 1.0f : weight_norm / adam_norm;  // lamb.py:99-102
   if (cm.y == 0 && threadIdx.x == 0) {

@@ -30,10 +30,13 @@ __global__ void __launch_bounds__(256) regress_epilogue_fwd_kernel(int N, const 
   for (int c = 0; c < 3; c++) xyz[i3 + c] = xyz_in[i3 + c] + v[c];
   opacity[n] = 1.0f / (1.0f + expf(-v[3]));
 #pragma unroll
-  for (int c = 0; c < 3; c++) scale[i3 + c] = fminf(expf(v[4 + c]), SCALE_MAX);
+  for (int c = 0; c < 3; c++) {  // clamp_max as a comparison: a NaN stays a NaN (fminf drops it)
+    const float e = expf(v[4 + c]);
+    scale[i3 + c] = e > SCALE_MAX ? SCALE_MAX : e;
+  }
   {
     const float nr = sqrtf(v[7] * v[7] + v[8] * v[8] + v[9] * v[9] + v[10] * v[10]);
-    const float inv = 1.0f / fmaxf(nr, NORM_EPS);
+    const float inv = 1.0f / (nr < NORM_EPS ? NORM_EPS : nr);  // clamp_min as a comparison: a NaN norm stays NaN
 #pragma unroll
     for (int c = 0; c < 4; c++) rot[4 * (size_t)n + c] = v[7 + c] * inv;
   }
@@ -74,7 +77,9 @@ __global__ void __launch_bounds__(256) regress_epilogue_bwd_kernel(int N, const 
 #pragma unroll
   for (int c = 0; c < 3; c++) {
     const float e = expf(v[4 + c]);
-    g[4 + c] = (g_scale && e <= SCALE_MAX) ? g_scale[i3 + c] * e : 0.f;  // clamp_max passes the gradient where it is inactive
+    // clamp_max passes the gradient where it is inactive; where it is active the reference multiplies its zero by e (exp's
+    // backward): 0 for a finite e, NaN for e = inf or NaN
+    g[4 + c] = g_scale ? (e <= SCALE_MAX ? g_scale[i3 + c] * e : 0.f * e) : 0.f;
   }
   {
     const float nr = sqrtf(v[7] * v[7] + v[8] * v[8] + v[9] * v[9] + v[10] * v[10]);
@@ -83,7 +88,7 @@ __global__ void __launch_bounds__(256) regress_epilogue_bwd_kernel(int N, const 
 #pragma unroll
       for (int c = 0; c < 4; c++) go[c] = g_rot[4 * (size_t)n + c];
     }
-    if (nr > NORM_EPS) {
+    if (!(nr <= NORM_EPS)) {  // (a NaN norm takes the general branch and stays NaN)
       const float inv = 1.0f / nr;
       const float d = (v[7] * go[0] + v[8] * go[1] + v[9] * go[2] + v[10] * go[3]) * inv * inv;
 #pragma unroll

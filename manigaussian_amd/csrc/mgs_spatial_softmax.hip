@@ -36,7 +36,7 @@ constexpr int SS_STRIDE = SS_THREADS * 4;   // elements between two consecutive 
 constexpr int SS_MAX_SLICES = 64;
 constexpr int SS_TARGET_BLOCKS = 2048;      // 256 CUs x 8 workgroups of 4 waves
 constexpr int SS_MIN_SLICE_VEC = 512;       // a slice is not cut below 2 vectors per lane
-constexpr int SS_REC = 8;                   // floats per slice record: m, index, s, sa, sb, sc, (two unused)
+constexpr int SS_REC = 8;                   // floats per slice record: m, index, s, sa, sb, sc, 1 if the slice holds a NaN, (unused)
 constexpr int SS_STATS = 6;                 // floats per row: m, sum, E_x, E_y, E_z, argmax (bits of a uint32)
 constexpr uint32_t SS_NO_INDEX = 0xffffffffu;
 
@@ -213,7 +213,16 @@ __global__ __launch_bounds__(SS_THREADS) void ss_fwd_kernel(SsGeom g, const floa
   }
   __shared__ SsPart wave_part[SS_THREADS / 64];
   if ((tid & 63u) == 0) wave_part[tid >> 6] = p;
-  __syncthreads();
+  // The running maximum is fmaxf's, which drops a NaN: right for the softmax, whose sums turn NaN by themselves, wrong for the
+  // max-pool, which is NaN in nn.AdaptiveMaxPool3d.  The sum tells, at no cost to the pass: a slice that holds a NaN has a NaN sum
+  // (so has one with a +inf: inf - inf in the exponent).  Only then the workgroup reads its slice once more and looks for a NaN.
+  int has_nan = 0;
+  if (__syncthreads_or(p.s != p.s ? 1 : 0)) {
+    const uint32_t begin = slice == 0 ? 0u : r.head + 4u * r.v0, end = slice == g.slices - 1 ? g.N : r.head + 4u * r.v1;
+    int mine = 0;
+    for (uint32_t i = begin + tid; i < end; i += SS_THREADS) mine |= x[i] != x[i] ? 1 : 0;
+    has_nan = __syncthreads_or(mine);
+  }
   if (tid == 0) {
     p = wave_part[0];
 #pragma unroll
@@ -221,7 +230,7 @@ __global__ __launch_bounds__(SS_THREADS) void ss_fwd_kernel(SsGeom g, const floa
     ssf4* rec = reinterpret_cast<ssf4*>(records + (size_t)blockIdx.x * SS_REC);
     ssf4 lo, hi;
     lo.x = p.m; lo.y = __uint_as_float(p.idx); lo.z = p.s; lo.w = p.sa;
-    hi.x = p.sb; hi.y = p.sc; hi.z = 0.f; hi.w = 0.f;
+    hi.x = p.sb; hi.y = p.sc; hi.z = has_nan ? 1.f : 0.f; hi.w = 0.f;
     rec[0] = lo;
     rec[1] = hi;
   }
@@ -243,8 +252,10 @@ __global__ __launch_bounds__(SS_THREADS) void ss_combine_kernel(SsGeom g, uint32
   float m = -INFINITY;
   uint32_t idx = SS_NO_INDEX;
   double s = 0, sa = 0, sb = 0, sc = 0;
+  bool has_nan = false;
   for (uint32_t j = 0; j < g.slices; ++j, rec += SS_REC) {
     const float mj = rec[0];
+    has_nan |= rec[6] != 0.f;
     const uint32_t ij = __float_as_uint(rec[1]);
     const float mn = fmaxf(m, mj);
     const float ms = mn == -INFINITY ? 0.f : mn;
@@ -261,7 +272,10 @@ __global__ __launch_bounds__(SS_THREADS) void ss_combine_kernel(SsGeom g, uint32
   const uint32_t b = row / g.C, c = row - b * g.C;
   float* kp = keypoints + (int64_t)b * kp_stride + 3 * (int64_t)c;
   kp[0] = ex; kp[1] = ey; kp[2] = ez;
-  if (maxpool) maxpool[(int64_t)b * mp_stride + c] = m;
+  if (maxpool) {
+    const float mp = has_nan ? __builtin_nanf("") : m;   // (the forward's flag: the maximum of a row that holds a NaN is NaN)
+    maxpool[(int64_t)b * mp_stride + c] = mp;   // (the statistics keep m)
+  }
   float* st = stats + (size_t)row * SS_STATS;
   st[0] = m; st[1] = (float)s; st[2] = ex; st[3] = ey; st[4] = ez; st[5] = __uint_as_float(idx);
 }
@@ -308,6 +322,10 @@ __global__ __launch_bounds__(SS_THREADS) void ss_bwd_kernel(SsGeom g, const floa
     const float* gk = g_kp ? g_kp + (int64_t)b * gk_stride + 3 * (int64_t)c : nullptr;
     R.gx = gk ? gk[0] : 0.f; R.gy = gk ? gk[1] : 0.f; R.gz = gk ? gk[2] : 0.f;
     R.gm = g_max ? g_max[(int64_t)b * gm_stride + c] : 0.f;
+    // A NaN or infinite keypoint gradient makes the whole row's gradient NaN in the reference: its softmax backward subtracts
+    // sum_j g_j p_j, which is then inf - inf or NaN.  g (pos - E) alone would give +-inf.  (g - g is 0 for a finite g, else NaN,
+    // and R.ps > 0 keeps its bits when 0 is added.)
+    R.ps += (R.gx - R.gx) + (R.gy - R.gy) + (R.gz - R.gz);
     R.ax = ss_axis(g.D); R.ay = ss_axis(g.H); R.az = ss_axis(g.W);
   }
 

@@ -141,11 +141,23 @@ __device__ __forceinline__ float vol_lerp(float a, float b, float t) { return fm
 __device__ __forceinline__ float vol_column(const VolRow& R, uint32_t i) {
   return vol_lerp(vol_lerp(R.r[0][i], R.r[1][i], R.ly), vol_lerp(R.r[2][i], R.r[3][i], R.ly), R.lz);
 }
+// The same sample as a sum of weighted taps, the form F.interpolate computes: with an infinite tap a, a + t (b - a) is inf - inf =
+// NaN where (1 - t) a + t b is the infinity.  Taken only where the lerp form gave a NaN, so finite volumes keep their bits.
+__device__ __forceinline__ float vol_mix(float a, float b, float t) { return (1.f - t) * a + t * b; }
+__device__ __forceinline__ float vol_column_mix(const VolRow& R, uint32_t i) {
+  return vol_mix(vol_mix(R.r[0][i], R.r[1][i], R.ly), vol_mix(R.r[2][i], R.r[3][i], R.ly), R.lz);
+}
 template <bool COPY>
 __device__ __forceinline__ float vol_sample(const VolGeom& g, const VolRow& R, uint32_t ox) {
   if (COPY) return R.r[0][vol_unpad(ox, g.W, g.pad)];
   const VolTap x = vol_tap(ox, g.W, g);
   return vol_lerp(vol_column(R, x.i0), vol_column(R, x.i1), x.lam);
+}
+// (ox goes through an opaque move: the compiler must not keep the first form's taps in registers for this one)
+__device__ __forceinline__ float vol_sample_mix(const VolGeom& g, const VolRow& R, uint32_t ox) {
+  asm volatile("" : "+v"(ox));
+  const VolTap x = vol_tap(ox, g.W, g);
+  return vol_mix(vol_column_mix(R, x.i0), vol_column_mix(R, x.i1), x.lam);
 }
 
 template <bool COPY>
@@ -166,6 +178,12 @@ __global__ __launch_bounds__(VOL_THREADS) void vol_fwd_kernel(VolGeom g, float* 
       v.y = vol_sample<COPY>(g, R, ox + 1);
       v.z = vol_sample<COPY>(g, R, ox + 2);
       v.w = vol_sample<COPY>(g, R, ox + 3);
+      if (!COPY && ((v.x != v.x) | (v.y != v.y) | (v.z != v.z) | (v.w != v.w))) {   // a NaN or an infinity among the taps
+        v.x = vol_sample_mix(g, R, ox);
+        v.y = vol_sample_mix(g, R, ox + 1);
+        v.z = vol_sample_mix(g, R, ox + 2);
+        v.w = vol_sample_mix(g, R, ox + 3);
+      }
     }
     *reinterpret_cast<volf4*>(out + e) = v;
     return;
@@ -176,6 +194,7 @@ __global__ __launch_bounds__(VOL_THREADS) void vol_fwd_kernel(VolGeom g, float* 
   for (uint32_t j = 0; j < 4; ++j) {
     if (j < count) {
       t[j] = vol_sample<COPY>(g, R, ox);
+      if (!COPY && t[j] != t[j]) t[j] = vol_sample_mix(g, R, ox);
       if (++ox == g.Wo && j + 1 < count) {
         ox = 0;
         if (++oy == g.Ho) {

@@ -1089,6 +1089,32 @@ int mgs_debug_binning_layout(const MgsRasterArgs* a, int32_t V, size_t* keys_uns
  * the compact keys_unsorted above. */
 int mgs_debug_direct_keys(const MgsRasterArgs* a, int32_t V, size_t* keys, int32_t* stride);
 
+/* Diagnostic, host code only (an additive export, ABI v17): every region the geom, img and binning workspaces of a forward
+ * are carved into, in carving order per workspace -- computed by the carving functions the kernels' host code uses.  `a` = the
+ * forward's arguments (shape, M, the three byte counts, binning_capacity / chunk_pool, opt; its pointers are not read), V as
+ * above.  kind: MGS_REGION_FLOAT if no kernel derives an address, a loop bound, an LDS index or a sort bucket from the region's
+ * words when it reads them legitimately; MGS_REGION_INDEX otherwise and in doubt (the table, with each region's
+ * writer, reader and what part is written).  A test that dirties workspaces may put any bytes into a FLOAT region and nothing
+ * but words of the same layout into an INDEX region.  The last entry is the direct keys (mgs_debug_direct_keys) where this
+ * forward's preprocess writes them: alias = 1 if they lie inside the two key arrays listed before them, 0 if behind the carved
+ * arrays.  Writes min(*count, max_regions) entries; max_regions = 0 only counts. */
+#define MGS_REGION_FLOAT 0
+#define MGS_REGION_INDEX 1
+#define MGS_WORKSPACE_GEOM 0
+#define MGS_WORKSPACE_IMG 1
+#define MGS_WORKSPACE_BINNING 2
+typedef struct MgsWorkspaceRegion {
+  char name[24];
+  int32_t workspace; /* MGS_WORKSPACE_* */
+  int32_t kind;      /* MGS_REGION_* */
+  int32_t alias;     /* 1: overlaps regions listed before it */
+  int32_t pad_;
+  size_t offset;     /* bytes from the start of its workspace */
+  size_t bytes;
+} MgsWorkspaceRegion;
+int mgs_debug_workspace_regions(const MgsRasterArgs* a, int32_t V, MgsWorkspaceRegion* out, int32_t max_regions,
+                                int32_t* count);
+
 /* Diagnostic: with MgsOptions.dbg = 256 the render forward stamps s_memtime per (workgroup < 512, wave, phase);
  * this copies the 512 * 16 * 24 uint64 stamps of the last forward to `host` (scripts/trace_fwd.py prints the timeline). */
 int mgs_debug_read_trace(unsigned long long* host, size_t count);

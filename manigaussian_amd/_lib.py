@@ -50,6 +50,15 @@ class MgsView(ctypes.Structure):
                 ("campos", c_fp)]
 
 
+class MgsWorkspaceRegion(ctypes.Structure):
+    _fields_ = [("name", ctypes.c_char * 24), ("workspace", c_i32), ("kind", c_i32), ("alias", c_i32), ("pad_", c_i32),
+                ("offset", c_sz), ("bytes", c_sz)]
+
+
+REGION_FLOAT, REGION_INDEX = 0, 1                       # MGS_REGION_*
+WORKSPACE_NAMES = ("geom", "img", "binning")            # MGS_WORKSPACE_*
+
+
 class MgsAttentionArgs(ctypes.Structure):
     _fields_ = [("B", c_i32), ("H", c_i32), ("Nq", c_i32), ("Nk", c_i32), ("D", c_i32), ("dropout_p", ctypes.c_float),
                 ("q", c_fp), ("k", c_fp), ("v", c_fp), ("mask", c_fp), ("rng_state", c_fp)] + \
@@ -291,6 +300,8 @@ _EXPORTS = {
     "mgs_debug_binning_layout": (ctypes.c_int, [ctypes.POINTER(MgsRasterArgs), c_i32] + [ctypes.POINTER(c_sz)] * 3 +
                                  [ctypes.POINTER(c_i32)]),
     "mgs_debug_direct_keys": (ctypes.c_int, [ctypes.POINTER(MgsRasterArgs), c_i32, ctypes.POINTER(c_sz), ctypes.POINTER(c_i32)]),
+    "mgs_debug_workspace_regions": (ctypes.c_int, [ctypes.POINTER(MgsRasterArgs), c_i32, ctypes.POINTER(MgsWorkspaceRegion), c_i32,
+                                                   ctypes.POINTER(c_i32)]),
     "mgs_debug_read_trace": (ctypes.c_int, [ctypes.c_void_p, c_sz]),
     "mgs_debug_read_trace_bwd": (ctypes.c_int, [ctypes.c_void_p, c_sz]),
     "mgs_debug_read_trace_bin": (ctypes.c_int, [ctypes.c_void_p, c_sz]),
@@ -451,6 +462,16 @@ def fill_options(a, opts=None):
     q.tight_bins, q.fast_exp, q.exact_cull, q.bin_mode = o["tight_bins"], o["fast_exp"], o["exact_cull"], o["bin_mode"]
     q.seg, q.gm_waves, q.dbg, q.table_init = o["seg"], o["gm_waves"], o["dbg"], o["table_init"]
     return o if opts is not None else dict(o)
+
+
+def workspace_regions(a, V=0):
+    """mgs_debug_workspace_regions: [(workspace name, region name, byte offset, bytes, kind, alias)] of a forward's three
+    workspaces in carving order (a: its MgsRasterArgs; host code only, no device needed)."""
+    L = lib()
+    out, n = (MgsWorkspaceRegion * 32)(), c_i32(0)
+    check(L.mgs_debug_workspace_regions(ctypes.byref(a), V, out, 32, ctypes.byref(n)), "mgs_debug_workspace_regions")
+    return [(WORKSPACE_NAMES[r.workspace], r.name.decode(), int(r.offset), int(r.bytes), int(r.kind), int(r.alias))
+            for r in out[:n.value]]
 
 
 def profile_read(reset: bool = True):

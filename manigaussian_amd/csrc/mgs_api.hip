@@ -883,6 +883,74 @@ int mgs_debug_direct_keys(const MgsRasterArgs* a, int32_t V, size_t* keys, int32
   return MGS_OK;
 }
 
+// Diagnostic (host code only): every region the three workspaces of `a` are carved into, read off the carve_* calls
+// themselves (CarveLog), named and classified in carving order.  FLOAT: no kernel derives an address, a loop bound, an LDS
+// index or a sort bucket from the region's words when it reads them legitimately (DESIGN.md 8b holds the table and the
+// reasons); everything else, and everything in doubt, is INDEX.
+struct RegionName { const char* name; int kind; };
+static const RegionName kGeomRegions[] = {
+    {"depths", MGS_REGION_INDEX}, {"rec", MGS_REGION_INDEX},     {"rect", MGS_REGION_INDEX},     {"rgb", MGS_REGION_FLOAT},
+    {"cov3D", MGS_REGION_FLOAT},  {"clamped", MGS_REGION_INDEX}, {"blk_base", MGS_REGION_INDEX}};
+static const RegionName kImgRegions[] = {{"final_T", MGS_REGION_FLOAT},
+                                         {"ranges", MGS_REGION_INDEX},
+                                         {"tables", MGS_REGION_INDEX},  // flags | tile_hist | seg_base | ref_count
+                                         {"ready", MGS_REGION_INDEX},
+                                         {"cursor", MGS_REGION_INDEX}};
+static const RegionName kBinRegions[] = {
+    {"keys_unsorted", MGS_REGION_INDEX}, {"keys", MGS_REGION_INDEX},       {"point_list", MGS_REGION_INDEX},
+    {"seg_desc", MGS_REGION_INDEX},      {"round_base", MGS_REGION_INDEX}, {"last_chunk", MGS_REGION_INDEX},
+    {"nsurv", MGS_REGION_INDEX},         {"surv", MGS_REGION_INDEX},       {"T_end", MGS_REGION_FLOAT},
+    {"T_mid", MGS_REGION_FLOAT},         {"last_pos", MGS_REGION_INDEX},   {"q", MGS_REGION_FLOAT},
+    {"partial", MGS_REGION_FLOAT}};
+
+int mgs_debug_workspace_regions(const MgsRasterArgs* a, int32_t V, MgsWorkspaceRegion* out, int32_t max_regions,
+                                int32_t* count) {
+  if (!a || a->W <= 0 || a->H <= 0 || a->P <= 0 || V < 0 || V > MAX_VIEWS || !count || (max_regions > 0 && !out)) {
+    set_error("workspace_regions: bad argument");
+    return MGS_ERR_INVALID_ARG;
+  }
+  const Pass s = pass_of(a, V);
+  const BinShape bs = bin_shape(a, s.T, s.F);
+  if (bs.cap < 0) { set_error("workspace_regions: binning workspace smaller than its fixed part"); return MGS_ERR_WORKSPACE; }
+  char* const base = reinterpret_cast<char*>(ALIGN);  // (a non-null dummy base: nothing is dereferenced)
+  CarveLog lg, li, lb;
+  (void)carve_geom(base, s.P, a->M, s.T, s.V, nullptr, &lg);
+  (void)carve_img(base, a->W, s.H, nullptr, &li);
+  size_t bin_total = 0;
+  (void)carve_binning(base, bs.cap, s.T, s.F, bs.pool, nullptr, &bin_total, &lb);
+  constexpr int NG = sizeof(kGeomRegions) / sizeof(RegionName), NI = sizeof(kImgRegions) / sizeof(RegionName),
+                NB = sizeof(kBinRegions) / sizeof(RegionName);
+  if (lg.n != NG || li.n != NI || lb.n != NB) {
+    set_error("workspace_regions: the region names are out of step with the carving (%d/%d, %d/%d, %d/%d)", lg.n, NG, li.n, NI,
+              lb.n, NB);
+    return MGS_ERR_INVALID_ARG;
+  }
+  int n = 0;
+  auto put = [&](int ws, const RegionName& r, size_t off, size_t bytes, int alias) {
+    if (n < max_regions) {
+      MgsWorkspaceRegion& o = out[n];
+      memset(&o, 0, sizeof(o));
+      strncpy(o.name, r.name, sizeof(o.name) - 1);
+      o.workspace = ws; o.kind = r.kind; o.alias = alias; o.offset = off; o.bytes = bytes;
+    }
+    n++;
+  };
+  for (int i = 0; i < NG; i++) put(MGS_WORKSPACE_GEOM, kGeomRegions[i], lg.off[i], lg.bytes[i], 0);
+  for (int i = 0; i < NI; i++) put(MGS_WORKSPACE_IMG, kImgRegions[i], li.off[i], li.bytes[i], 0);
+  for (int i = 0; i < NB; i++) put(MGS_WORKSPACE_BINNING, kBinRegions[i], lb.off[i], lb.bytes[i], 0);
+  // the direct keys (direct_region): inside the two key arrays (an alias of regions listed above) or behind the carved arrays
+  MgsRasterArgs c = *a;
+  c.binning = base;
+  if (const uint64_t* dk = direct_region(&c, bs, s, options_of(a))) {
+    const size_t off = (size_t)(reinterpret_cast<const char*>(dk) - base);
+    const RegionName r = {"direct_keys", MGS_REGION_INDEX};
+    put(MGS_WORKSPACE_BINNING, r, off, direct_keys_needed((size_t)s.P, s.V, s.T) * sizeof(uint64_t), off < bin_total ? 1 : 0);
+  }
+  *count = n;
+  if (n > max_regions && max_regions > 0) { set_error("workspace_regions: %d regions, room for %d", n, max_regions); return MGS_ERR_INVALID_ARG; }
+  return MGS_OK;
+}
+
 int mgs_profile_num_stages(void) { return ST_COUNT; }
 const char* mgs_profile_stage_name(int i) { return (i >= 0 && i < ST_COUNT) ? kStageNames[i] : ""; }
 

@@ -26,14 +26,24 @@ constexpr int SEG_MIN = 512;     // smallest selectable sort segment (sizes the 
 constexpr size_t ALIGN = 256;
 inline size_t align_up(size_t v) { return (v + ALIGN - 1) & ~(ALIGN - 1); }
 
+// What a carving took, in order: {byte offset, bytes} of every take() (mgs_debug_workspace_regions reads the layout off the
+// carve_* functions themselves; nullptr everywhere else).
+struct CarveLog {
+  static constexpr int MAX = 16;
+  int n = 0;
+  size_t off[MAX], bytes[MAX];
+};
+
 struct Carver {
   char* base;
   size_t off;
-  explicit Carver(void* p) : base(reinterpret_cast<char*>(p)), off(0) {}
+  CarveLog* log;
+  explicit Carver(void* p, CarveLog* l = nullptr) : base(reinterpret_cast<char*>(p)), off(0), log(l) {}
   template <typename T>
   T* take(size_t count) {
     off = align_up(off);
     T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    if (log && log->n < CarveLog::MAX) { log->off[log->n] = off; log->bytes[log->n] = count * sizeof(T); log->n++; }
     off += count * sizeof(T);
     return p;
   }
@@ -130,8 +140,8 @@ inline size_t preprocess_blocks(size_t P, int V) {
   const size_t v = V > 0 ? (size_t)V : 1, Pg = (P + v - 1) / v, pb = (size_t)pre_block(Pg);
   return v * ((Pg + pb - 1) / pb);
 }
-inline GeomView carve_geom(void* p, int P, int M, int T, int V, size_t* total) {
-  Carver c(p);
+inline GeomView carve_geom(void* p, int P, int M, int T, int V, size_t* total, CarveLog* log = nullptr) {
+  Carver c(p, log);
   GeomView g;
   size_t Pa = P > 0 ? (size_t)P : 1;
   g.depths = c.take<float>(Pa);
@@ -147,8 +157,8 @@ inline GeomView carve_geom(void* p, int P, int M, int T, int V, size_t* total) {
   return g;
 }
 
-inline ImgView carve_img(void* p, int W, int H, size_t* total) {
-  Carver c(p);
+inline ImgView carve_img(void* p, int W, int H, size_t* total, CarveLog* log = nullptr) {
+  Carver c(p, log);
   ImgView v;
   size_t N = (size_t)W * H;
   size_t T = (size_t)((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);
@@ -177,8 +187,9 @@ inline uint32_t chunk_pool_max(size_t R, int T) { return (uint32_t)(4 * ((R + CH
 inline size_t round_table_entries(size_t R, int T) { return 4 * (R / 512 + 2 * (size_t)T + 2); }
 
 // R: capacity of the instance list; pool: chunk records (0: the worst case for R).
-inline BinView carve_binning(void* p, int R, int T, int F, uint32_t pool, ChunkView* cv, size_t* total) {
-  Carver c(p);
+inline BinView carve_binning(void* p, int R, int T, int F, uint32_t pool, ChunkView* cv, size_t* total,
+                             CarveLog* log = nullptr) {
+  Carver c(p, log);
   BinView b;
   size_t Ra = R > 0 ? (size_t)R : 1;
   b.keys_unsorted = c.take<uint64_t>(Ra);

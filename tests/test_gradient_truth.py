@@ -154,9 +154,18 @@ def _hip_scene(tag, s, T, few=None):
     """A scene tuple (sc, cam, kw, dC, dF) through util.run_hip under the options in force, gated against its truth T (few:
     the cap on the NUMBER of fragile pixels where a share of the image says nothing).  Returns what run_hip returned."""
     sc, cam, kw, dC, dF = s
+    out = util.run_hip(sc, cam, dC, dF, kw["sh_degree"], bool(kw["include_feature"]), tuple(kw["bg"].tolist()),
+                       scale_modifier=kw["scale_modifier"])
+    _gate_scene(tag, s, T, out, few)
+    return out
+
+
+def _gate_scene(tag, s, T, out, few=None):
+    """_hip_scene's gates on what a run of the scene returned, out = (color, feature, radii, gradients by leaf name) as
+    util.run_hip returns them (tests/test_rasterizer_dirty_workspace.py gates its own runs with it)."""
+    kw = s[2]
     inc = bool(kw["include_feature"])
-    ch, fh, rh, gh = util.run_hip(sc, cam, dC, dF, kw["sh_degree"], inc, tuple(kw["bg"].tolist()),
-                                  scale_modifier=kw["scale_modifier"])
+    ch, fh, rh, gh = out
     assert torch.equal(rh, T.radii), "radii differ"
     T = gt.follow(T, ch, fh if inc else None)
     gt.gate_image(tag, "color", ch, T.images["color"], T.fragile_px, T.image_yard["color"], max_fragile_pixels=few)
@@ -168,7 +177,6 @@ def _hip_scene(tag, s, T, few=None):
     got = {util.GRAD_KEYS[k]: v for k, v in gh.items() if util.GRAD_KEYS[k] in T.grads}
     assert set(got) == set(T.grads), (sorted(got), sorted(T.grads))
     gt.gate_gradients(tag, T, got)
-    return ch, fh, rh, gh
 
 
 def _hip_case(tag, name):

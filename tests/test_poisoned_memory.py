@@ -5,9 +5,10 @@ must have the clean run's bits and no non-finite element the clean run has not. 
 the ops compute is the business of their own test files.  This is the test `_ops.workspace`'s docstring and the header of
 csrc/mgs_records.hip name.
 
-Not enrolled: the rasterizer (_C.py, rasterizer.py).  Its binning buffers hold keys, offsets and counts that kernels use as addresses;
-test_gpu_parity.py, test_edge_scenes.py and test_set_batch.py run it over changing scenes.  NOT_ENROLLED lists it and the other
-modules that call torch.empty without being an op.
+Not enrolled HERE: the rasterizer (_C.py, rasterizer.py, views.py).  Its binning buffers hold keys, offsets and counts that kernels use
+as addresses, so a 0xFF fill could turn a stale read into an out-of-bounds access; tests/test_rasterizer_dirty_workspace.py holds it to
+the same property with fills chosen by the kind of region (zeros, a donor call's bytes, 0xFF / 0x7F over the float regions only:
+tests/dirty_workspace.py).  NOT_ENROLLED lists it and the other modules that call torch.empty without being an op.
 
 Who writes and who first reads every region, read off the host code and the kernels before any of this ran on a GPU ("ws": the region
 of `_ops.workspace`; "-": never read by a kernel):
@@ -128,8 +129,8 @@ ALLOCATING = {
     "losses": ["test_rendering_loss"], "photometric": ["test_photometric_loss"], "optim": ["test_fused_lamb"],
 }
 NOT_ENROLLED = {
-    "_C": "the rasterizer: its binning buffers hold keys, offsets and counts that kernels use as addresses; test_gpu_parity.py, "
-          "test_edge_scenes.py and test_set_batch.py run it over changing scenes",
+    "_C": "the rasterizer: its binning buffers hold keys, offsets and counts that kernels use as addresses; "
+          "test_rasterizer_dirty_workspace.py dirties its workspaces and results with fills chosen by the kind of region",
     "parallel": "host staging buffers and communication results that a collective fills; no kernel of the library",
     "_ops": "the workspace's own allocation: what poisoned() fills",
     "_conv": "backward_begin allocates dx, dw and db for pointwise, narrow, dense and patch, which are enrolled",

@@ -17,6 +17,8 @@ import os
 import numpy as np
 import torch
 
+from numerics import same_bits  # noqa: F401  (re-exported: the tests and the tools reach them through this module)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN_DIR = os.path.join(ROOT, "tests", "golden", "abn")
 NAMES_FILE = os.path.join(GOLDEN_DIR, "stem_state_dict_names.txt")
@@ -194,10 +196,6 @@ def load_fixture(case):
 def bound(ref_err, truth):
     """Largest allowed |ours - truth|."""
     return max(FACTOR * ref_err, FACTOR * FLOOR) * truth.abs().max().item()
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and bool((a.contiguous().view(torch.int32) == b.contiguous().view(torch.int32)).all())
 
 
 def stem_state_dict_names():

@@ -18,6 +18,8 @@ import types
 import numpy as np
 import torch
 
+from numerics import same_bits  # noqa: F401  (re-exported: the tests and the tools reach them through this module)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN_DIR = os.path.join(ROOT, "tests", "golden", "attention")
 REF_FILE = os.path.join(os.environ.get("MGS_REFERENCE_ROOT", "/root/reference"), "agents", "manigaussian_bc",
@@ -283,7 +285,3 @@ def bounds(case, f=None):
         else:
             res[n] = (ZERO_BOUND * other, 0.0, 0.0)
     return res
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and bool((a.contiguous().view(torch.int32) == b.contiguous().view(torch.int32)).all())

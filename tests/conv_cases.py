@@ -10,7 +10,8 @@ A family's own file keeps its CASES table, make_inputs, torchs, its kernels' til
 """
 import torch
 
-from abn_cases import FACTOR, FLOOR, REF_ERR_CEILING, bound, same_bits  # noqa: F401
+from abn_cases import FACTOR, FLOOR, REF_ERR_CEILING, bound  # noqa: F401
+from numerics import same_bits  # noqa: F401
 
 
 def has_bias(cases, case):

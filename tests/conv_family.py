@@ -4,14 +4,12 @@ test_patch_conv.py, and test_poisoned_memory.py, which walks all five) and of th
 A family is a Family record in FAMILIES: its cases module, its C entry points, how a case's extra arguments reach its op, and what
 its backward is handed beside dx, dw and db.  Over that record this file holds once what every family's tests do: one forward +
 backward on the device, the comparison with the float64 truth, the same bits across runs and splits, only the requested gradients,
-views, the library calls counted, the graph tool's child process, the routing criterion, the bad-argument builder and the ABI check.
+views, the library calls counted, the graph tool's arguments, the routing criterion, the bad-argument builder and the ABI check.
 """
 import ctypes
 import importlib
 import os
 import re
-import subprocess
-import sys
 
 import torch
 
@@ -20,12 +18,13 @@ import dense_conv_cases
 import narrow_conv_cases
 import patch_conv_cases
 import pointwise_cases
-from conv_cases import FACTOR, FLOOR, same_bits
+from child import run_graph_tool
+from conv_cases import FACTOR, FLOOR
 from manigaussian_amd import _lib
+from numerics import dev, same_bits, spy
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mgsplat.h")
-GRAPH_TOOL = os.path.join(ROOT, "tests", "tools", "conv_graph_capture_check.py")
 ABI = 17
 ALL_NEEDS = ((True, False, False), (False, True, True), (False, False, True), (True, True, False), (False, False, False))
 
@@ -95,7 +94,7 @@ FAMILIES = {f.name: f for f in (
     # the padded gradient is allocated where dx is asked for
     Family("dense", dense_conv_cases, "mgs_dense_conv3d_", _dense, ("odd_k3", "up0_last_head"), splits=(1, 3, 64),
            watched=("dx", "dw", "db", "g_scratch"), also_given=lambda need: (need[0],)),
-    # the workspace is passed where dw or db is asked for (its graph tool is its own: tests/tools/patch_graph_capture_check.py)
+    # the workspace is passed where dw or db is asked for
     Family("patch", patch_conv_cases, "mgs_patch_conv3d_", patch_conv_cases.call, ("odd", "site_small"), splits=(1, 3, 64),
            watched=("dx", "dw", "db", "workspace"), also_given=lambda need: (need[1] or need[2],)),
 )}
@@ -215,10 +214,6 @@ def op_wins(entry, benchmark_may_be_missing=False):
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------------
-def dev():
-    return torch.device("cuda:0")
-
-
 def run(family, case, split=0, need=(True, True, True), **given):
     """{y, dx, dw, db}: CPU tensors of one forward + backward of the op on the case's inputs (or on x / w / b / g given, on the
     device)."""
@@ -307,15 +302,9 @@ def backward_positions(family):
 def count_calls(monkeypatch, family):
     """Replaces the family's entry points on the library object by wrappers that record (name,) per call, and for a backward (name,
     family.watched given ...)."""
-    L, calls, at = _lib.lib(), [], backward_positions(family)
-
-    def wrap(name, real):
-        def f(*a):
-            calls.append((name[len(family.prefix):],) + tuple(bool(a[i]) for i in at.get(name, ())))
-            return real(*a)
-        return f
-    for name in family.names[1:]:
-        monkeypatch.setattr(L, name, wrap(name, getattr(L, name)))
+    calls, at = [], backward_positions(family)
+    spy(_lib.lib(), family.names[1:], monkeypatch,
+        on_call=lambda name, a: calls.append((name[len(family.prefix):],) + tuple(bool(a[i]) for i in at.get(name, ()))))
     return calls
 
 
@@ -377,6 +366,4 @@ def check_views(family, case):
 
 def graph_capture(*tool_args):
     """The graph tool in a child process: stream capture is process-wide state."""
-    r = subprocess.run(["timeout", "-k", "10", "150", sys.executable, GRAPH_TOOL] + list(tool_args), capture_output=True, text=True,
-                       timeout=170)
-    assert r.returncode == 0 and "GRAPH_OK" in r.stdout, f"exit {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
+    run_graph_tool("conv_graph_capture_check.py", *tool_args)

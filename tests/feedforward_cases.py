@@ -20,6 +20,7 @@ import torch.nn.functional as F
 from torch import nn
 
 import attention_cases as ac
+from numerics import rel_err, same_bits  # noqa: F401  (re-exported: the tests and the tools reach them through this module)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN_DIR = os.path.join(ROOT, "tests", "golden", "feedforward")
@@ -57,19 +58,8 @@ SPLITS = (1, 2, 3, 64)
 SPLIT_CASES = ("r257_d512", "r257_m6")
 
 
-def rel_err(got, truth):
-    """max|got - truth| over max|truth| (the absolute error for an all-zero truth)."""
-    mag = truth.abs().max().item()
-    d = (got.double().cpu() - truth.double().cpu()).abs().max().item()
-    return d / mag if mag > 0 else d
-
-
 def bound(ref_err):
     return FACTOR * max(ref_err, FLOOR)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and bool((a.contiguous().view(torch.int32) == b.contiguous().view(torch.int32)).all())
 
 
 # ---- the two ops ------------------------------------------------------------------------------------------------------------------

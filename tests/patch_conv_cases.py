@@ -1,4 +1,4 @@
-"""The patch-embedding family's cases and inputs for tests/test_patch_conv.py and tests/tools/patch_graph_capture_check.py -- TEST
+"""The patch-embedding family's cases and inputs for tests/test_patch_conv.py and tests/tools/conv_graph_capture_check.py -- TEST
 INFRASTRUCTURE.  The reference is torch's own act(F.conv3d(F.pad(x, (pad,) * 6, mode), w, b, stride=k)) on the CPU; how it is shared,
 its yardstick and the bound: tests/conv_cases.py.
 

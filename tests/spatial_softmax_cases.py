@@ -18,6 +18,8 @@ import os
 import numpy as np
 import torch
 
+from numerics import same_bits  # noqa: F401  (re-exported: the tests and the tools reach them through this module)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN_DIR = os.path.join(ROOT, "tests", "golden", "spatial_softmax")
 REF_FILE = os.path.join(os.environ.get("MGS_REFERENCE_ROOT", "/root/reference"), "helpers", "network_utils.py")
@@ -182,7 +184,3 @@ def bounds(case, f=None):
     f = load_fixture(case) if f is None else f
     e = f["ref_err"]
     return {"kp": kp_bound(e["kp"]), "dx": dx_bound(e["dx"], f["dx64"]), "dx_k": dx_bound(e["dx_k"], f["dx64_k"])}
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and bool((a.contiguous().view(torch.int32) == b.contiguous().view(torch.int32)).all())

@@ -16,14 +16,14 @@ import json
 import math
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import attention_cases as ac
+from child import run_graph_tool
+from numerics import dev
 
 gpu = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -246,10 +246,6 @@ def test_attention_refuses_cpu_tensors_and_other_head_sizes_and_loads_a_referenc
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------------
-def dev():
-    return torch.device("cuda:0")
-
-
 def build_module(case, dropout=None):
     from manigaussian_amd import Attention
     c = ac.CASES[case]
@@ -637,6 +633,4 @@ def test_forward_and_backward_never_hold_a_score_matrix():
 @gpu
 def test_forward_and_backward_captured_into_a_hip_graph():
     """In a child process: stream capture is process-wide state (tests/tools/attention_graph_capture_check.py)."""
-    tool = os.path.join(ROOT, "tests", "tools", "attention_graph_capture_check.py")
-    r = subprocess.run(["timeout", "-k", "10", "150", sys.executable, tool], capture_output=True, text=True, timeout=170)
-    assert r.returncode == 0 and "GRAPH_OK" in r.stdout, f"exit {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
+    run_graph_tool("attention_graph_capture_check.py")

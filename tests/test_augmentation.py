@@ -15,13 +15,12 @@ most about 4e-6 whatever the order of its sums and whether or not they are fused
 import ctypes
 import math
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+from child import run_graph_tool
 import se3_cases as sc
 
 gpu = pytest.mark.gpu
@@ -337,7 +336,4 @@ def test_the_module_draws_what_se3_draws_names_and_advances_by_one_per_call():
 @gpu
 def test_augmentation_then_voxelizer_captured_into_a_hip_graph():
     """In a child process: stream capture is process-wide state (tests/tools/se3_graph_capture_check.py)."""
-    tool = os.path.join(ROOT, "tests", "tools", "se3_graph_capture_check.py")
-    r = subprocess.run(["timeout", "-k", "10", "150", sys.executable, tool], capture_output=True, text=True, timeout=170)
-    print(r.stdout[-3000:], r.stderr[-3000:])
-    assert r.returncode == 0 and "GRAPH_OK" in r.stdout
+    run_graph_tool("se3_graph_capture_check.py")

@@ -19,6 +19,7 @@ import pytest
 import torch
 
 import embed_cases as ec
+from numerics import dev
 import util
 
 gpu = pytest.mark.gpu
@@ -226,10 +227,6 @@ def test_the_library_refuses_bad_arguments_before_any_launch():
 
 
 # ---- GPU --------------------------------------------------------------------------------------------------------------------------
-def dev():
-    return torch.device("cuda:0")
-
-
 def check_groups(tag, groups, got, truth, ref_err):
     """Every group of got within the rule's bound of truth; each figure is printed and reported before anything is asserted."""
     failed = []

@@ -10,16 +10,16 @@ On the GPU machine the reference does not exist: the full-size tests take the sa
 (abn_cases.restatement, pinned against the fixtures here) in float64 as the truth and in float32 as the yardstick.
 """
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import abn_cases as ac
+from child import run_graph_tool
 from manigaussian_amd import _lib
 from manigaussian_amd import encoder as enc
+from numerics import dev
 
 gpu = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -262,10 +262,6 @@ def test_the_routing_rule_matches_the_committed_measurement():
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------------
-def dev():
-    return torch.device("cuda:0")
-
-
 def run(t, case_or_slope, training=True, slices=0, x=None, hooks=None):
     """{quantity: CPU tensor} of one forward (+ backward) of the op on a fixture-shaped dict `t`; fresh running buffers (0, 1) unless
     `t` holds running_mean0 / running_var0."""
@@ -489,6 +485,4 @@ def test_the_drop_in_stem_fused_against_torchs_path(route):
 @gpu
 def test_forward_and_backward_captured_into_a_hip_graph():
     """In a child process: stream capture is process-wide state (tests/tools/abn_graph_capture_check.py)."""
-    tool = os.path.join(ROOT, "tests", "tools", "abn_graph_capture_check.py")
-    r = subprocess.run(["timeout", "-k", "10", "150", sys.executable, tool], capture_output=True, text=True, timeout=170)
-    assert r.returncode == 0 and "GRAPH_OK" in r.stdout, f"exit {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
+    run_graph_tool("abn_graph_capture_check.py")

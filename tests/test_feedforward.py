@@ -10,8 +10,6 @@ for the output and every gradient.  Torch's own ref_err is below 4e-7 at every c
 are checked by value.  At the production shapes the truth is float64 on the GPU and the yardstick torch's float32 run there.
 """
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -19,9 +17,12 @@ import torch
 import torch.nn.functional as F
 
 import attention_cases as ac
+from child import run_graph_tool
 import feedforward_cases as fc
+from numerics import dev, spy
 
 gpu = pytest.mark.gpu
+FUSED_ENTRIES = ("mgs_layernorm_forward", "mgs_layernorm_backward", "mgs_bias_geglu_forward", "mgs_bias_geglu_backward")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LN_NAMES = {"d0": "dx", "d1": "dweight", "d2": "dbias"}
 GG_NAMES = {"d0": "dh", "d1": "dbias"}
@@ -292,10 +293,6 @@ def test_the_drop_ins_routing_follows_the_recorded_medians():
 
 
 # ---- GPU -----------------------------------------------------------------------------------------------------------------------
-def dev():
-    return torch.device("cuda:0")
-
-
 def ours_ln(row_split=0):
     from manigaussian_amd import layer_norm
     return lambda x, w, b: layer_norm(x, w, b, fc.EPS, row_split=row_split)
@@ -339,10 +336,7 @@ def test_bias_geglu_cases_forward_and_gradients(case):
 @gpu
 def test_views_are_read_in_place_and_equal_their_copies(monkeypatch):
     from manigaussian_amd import _lib
-    seen = {}
-    for name in ("mgs_layernorm_forward", "mgs_layernorm_backward", "mgs_bias_geglu_forward", "mgs_bias_geglu_backward"):
-        real = getattr(_lib.lib(), name)
-        monkeypatch.setattr(_lib.lib(), name, (lambda *a, _r=real, _n=name: (seen.setdefault(_n, []).append(a), _r(*a))[1]))
+    seen = spy(_lib.lib(), FUSED_ENTRIES, monkeypatch)
     for kind, case, fn in (("ln", "strided", ours_ln()), ("geglu", "strided", ours_geglu()), ("ln", "expanded_g", ours_ln())):
         t = fc.truth(kind, case)
         seen.clear()
@@ -369,9 +363,7 @@ def test_views_are_read_in_place_and_equal_their_copies(monkeypatch):
 @gpu
 def test_frozen_parameters_get_dx_alone_without_partial_sums(monkeypatch):
     from manigaussian_amd import _lib, bias_geglu
-    calls = []
-    real = _lib.lib().mgs_layernorm_backward
-    monkeypatch.setattr(_lib.lib(), "mgs_layernorm_backward", lambda *a: (calls.append(a), real(*a))[1])
+    calls = spy(_lib.lib(), ["mgs_layernorm_backward"], monkeypatch)["mgs_layernorm_backward"]
     t, got = run_case("ln", "frozen")
     assert set(got) == {"out", "d0"} and len(calls) == 1
     dw, db, ws, ws_bytes = calls[0][9:13]
@@ -385,9 +377,7 @@ def test_frozen_parameters_get_dx_alone_without_partial_sums(monkeypatch):
     full = fc.run_op(ours_ln(), [x, w, b], t["g"], None, dev())
     assert fc.same_bits(free["d0"], full["d0"]) and fc.same_bits(free["d2"], full["d2"]) and fc.same_bits(free["d0"], got["d0"])
     # the GEGLU without a bias gradient
-    gcalls = []
-    greal = _lib.lib().mgs_bias_geglu_backward
-    monkeypatch.setattr(_lib.lib(), "mgs_bias_geglu_backward", lambda *a: (gcalls.append(a), greal(*a))[1])
+    gcalls = spy(_lib.lib(), ["mgs_bias_geglu_backward"], monkeypatch)["mgs_bias_geglu_backward"]
     tg = fc.truth("geglu", "r65_m130")
     a = fc.run_op(ours_geglu(), tg["inputs"], tg["g"], None, dev(), frozen=(1,))
     assert set(a) == {"out", "d0"} and gcalls[0][8] is None and gcalls[0][9] is None
@@ -447,16 +437,13 @@ def test_the_row_split_changes_no_bit_of_dx_and_keeps_the_sums_within_the_bound(
     assert fc.same_bits(auto["d0"], runs[1]["d0"])
 
 
-def route(monkeypatch, kernels, calls=None):
-    """The drop-ins' routing for this test: both ops through the kernels, or both through torch.  calls: a dict that counts the
+def route(monkeypatch, kernels, watch=False):
+    """The drop-ins' routing for this test: both ops through the kernels, or both through torch.  watch: returns the spy's record of the
     library's entries."""
     from manigaussian_amd import _lib, feedforward
     monkeypatch.setitem(feedforward.ROUTE, "layer_norm", kernels)
     monkeypatch.setitem(feedforward.ROUTE, "bias_geglu", kernels)
-    if calls is not None:
-        for name in ("mgs_layernorm_forward", "mgs_layernorm_backward", "mgs_bias_geglu_forward", "mgs_bias_geglu_backward"):
-            real = getattr(_lib.lib(), name)
-            monkeypatch.setattr(_lib.lib(), name, (lambda *a, _r=real, _n=name: (calls.__setitem__(_n, calls.get(_n, 0) + 1), _r(*a))[1]))
+    return spy(_lib.lib(), FUSED_ENTRIES, monkeypatch) if watch else None
 
 
 @gpu
@@ -465,8 +452,7 @@ def route(monkeypatch, kernels, calls=None):
 def test_module_fixtures_on_the_device(name, kernels, monkeypatch):
     """Whatever the shipped routing: once with both ops through the kernels, once with both left to torch."""
     import manigaussian_amd
-    calls = {}
-    route(monkeypatch, kernels, calls)
+    calls = route(monkeypatch, kernels, watch=True)
     f = fc.load_module_fixture(name)
     m = fc.fixture_module(manigaussian_amd, name)
     got = fc.run_module(m, f["x"], f["g"], torch.float32, dev(), context=f.get("context"))
@@ -474,7 +460,7 @@ def test_module_fixtures_on_the_device(name, kernels, monkeypatch):
     want = {"prenorm_ff": {"mgs_layernorm_forward": 1, "mgs_layernorm_backward": 1, "mgs_bias_geglu_forward": 1, "mgs_bias_geglu_backward": 1},
             "ff_odd": {"mgs_bias_geglu_forward": 1, "mgs_bias_geglu_backward": 1},
             "prenorm_context": {"mgs_layernorm_forward": 2, "mgs_layernorm_backward": 2}}[name]
-    assert calls == (want if kernels else {}), (name, kernels, calls)
+    assert {k: len(v) for k, v in calls.items()} == (want if kernels else {}), (name, kernels, calls)
 
 
 @gpu
@@ -561,6 +547,4 @@ def test_the_library_refuses_on_the_device_and_launches_nothing():
 @gpu
 def test_forward_and_backward_captured_into_a_hip_graph():
     """In a child process: stream capture is process-wide state (tests/tools/feedforward_graph_capture_check.py)."""
-    tool = os.path.join(ROOT, "tests", "tools", "feedforward_graph_capture_check.py")
-    r = subprocess.run(["timeout", "-k", "10", "150", sys.executable, tool], capture_output=True, text=True, timeout=170)
-    assert r.returncode == 0 and "GRAPH_OK" in r.stdout, f"exit {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
+    run_graph_tool("feedforward_graph_capture_check.py")

@@ -9,14 +9,12 @@ reaches is decided on the CPU by a model of the chunk walk over Oracle B's lists
 GPU through mgs_forward_stats: the three counts must be the model's wherever the model sits further than 1e-3 (relative)
 from every alive / dead decision -- a product of <= 2400 factors differs between two association orders by far less."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+from child import run_graph_tool
 import reachable_chunks_cases as rc
 import util
 from manigaussian_amd import _C, _lib
@@ -182,6 +180,4 @@ def test_eight_wave_form_whose_second_slot_starts_at_chunk_4(F):
 def test_skip_path_replays_bit_identically_from_a_captured_graph():
     """(a) under graph capture (tests/tools/reachable_chunks_graph_check.py, in a process of its own: stream capture is
     process-wide state): the replayed forward + backward reproduces the eager images bit for bit."""
-    tool = os.path.join(os.path.dirname(__file__), "tools", "reachable_chunks_graph_check.py")
-    r = subprocess.run([sys.executable, tool], capture_output=True, text=True, timeout=170)
-    assert r.returncode == 0 and "GRAPH_OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    run_graph_tool("reachable_chunks_graph_check.py", limit=170)

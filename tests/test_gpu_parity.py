@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+from child import run_graph_tool
 import util
 from manigaussian_amd import GaussianRasterizationSettings, GaussianRasterizer, _lib
 from manigaussian_amd import synthetic as syn
@@ -675,11 +676,7 @@ def test_forward_backward_captured_into_a_hip_graph_replays_bit_identically():
     """fwd + bwd through the public autograd API captured with torch.cuda.graph (tests/tools/graph_capture_check.py, in a
     process of its own: stream capture is process-wide state): the capture succeeds because the library never
     synchronises, replays reproduce the eager images bit for bit and follow in-place parameter updates."""
-    import subprocess
-    import sys
-    tool = os.path.join(os.path.dirname(__file__), "tools", "graph_capture_check.py")
-    r = subprocess.run([sys.executable, tool], capture_output=True, text=True, timeout=170)
-    assert r.returncode == 0 and "GRAPH_OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    run_graph_tool("graph_capture_check.py", limit=170)
 
 
 @pytest.mark.parametrize("path", GOLDEN, ids=[os.path.basename(p)[:-4] for p in GOLDEN])

@@ -8,12 +8,11 @@ F = 3 and 32, all three embed functions; the fused pass sums in another order an
 1e-5.  PSNR: 20 log10 of a 1e-5 relative change is 4e-5 dB -> 1e-4 dB absolute.
 """
 import os
-import subprocess
-import sys
 
 import pytest
 import torch
 
+from child import run_graph_tool
 import loss_cases as lc
 from manigaussian_amd import losses
 from manigaussian_amd import synthetic as syn
@@ -296,9 +295,7 @@ def test_render_loss_backward_captured_into_a_hip_graph_follows_targets_and_weig
     """tests/tools/loss_graph_capture_check.py in a process of its own (stream capture is process-wide state): render -> loss
     -> backward captured with torch.cuda.graph, replayed after the target images and the device-side weights were
     overwritten in place; the replay equals the eager step on the new targets and weights."""
-    tool = os.path.join(os.path.dirname(__file__), "tools", "loss_graph_capture_check.py")
-    r = subprocess.run([sys.executable, tool], capture_output=True, text=True, timeout=170)
-    assert r.returncode == 0 and "GRAPH_OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    run_graph_tool("loss_graph_capture_check.py", limit=170)
 
 
 # ---- without a GPU --------------------------------------------------------------------------------------------------------

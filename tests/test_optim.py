@@ -13,13 +13,12 @@ Discrete outcomes are exact: which branch the trust ratio took, a skipped parame
 zero_grad=True leaving the flat gradient buffer all zeros.
 """
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+from child import run_graph_tool
 import lamb_cases as lc
 
 gpu = pytest.mark.gpu
@@ -350,6 +349,4 @@ def test_the_step_never_synchronises_with_the_host():
 @gpu
 def test_manigaussian_step_with_the_optimizer_captured_into_a_hip_graph_follows_a_device_lr():
     """In a child process (stream capture is process-wide state) under its own time limit."""
-    tool = os.path.join(ROOT, "tests", "tools", "optim_graph_capture_check.py")
-    r = subprocess.run([sys.executable, tool], capture_output=True, text=True, timeout=170)
-    assert r.returncode == 0 and "GRAPH_OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    run_graph_tool("optim_graph_capture_check.py", limit=170)

@@ -8,8 +8,6 @@ import importlib
 import json
 import os
 import re
-import subprocess
-import sys
 
 import pytest
 import torch
@@ -24,9 +22,7 @@ pt = importlib.import_module("manigaussian_amd.patch")
 
 gpu = pytest.mark.gpu
 ROOT = cf.ROOT
-GRAPH_TOOL = os.path.join(ROOT, "tests", "tools", "patch_graph_capture_check.py")
 FAMILY = cf.FAMILIES["patch"]   # (the workspace is passed where dw or db is asked for)
-GRAPH_CASES = FAMILY.graph_cases
 BENCH_SHAPES = {"patchify_100": (128, 128, 100), "patchify_50": (128, 128, 50), "patchify_25": (128, 128, 25), "peract_100": (64, 64, 100)}
 
 
@@ -417,10 +413,8 @@ def test_the_block_routed_against_the_same_module_not_routed(switch, monkeypatch
 
 @gpu
 def test_forward_and_backward_captured_into_a_hip_graph():
-    """In a child process: stream capture is process-wide state (tests/tools/patch_graph_capture_check.py)."""
-    r = subprocess.run(["timeout", "-k", "10", "150", sys.executable, GRAPH_TOOL] + list(GRAPH_CASES), capture_output=True, text=True,
-                       timeout=170)
-    assert r.returncode == 0 and "GRAPH_OK" in r.stdout, f"exit {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
+    """In a child process: stream capture is process-wide state (tests/tools/conv_graph_capture_check.py)."""
+    cf.graph_capture(FAMILY.name)
 
 
 @gpu

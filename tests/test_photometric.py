@@ -7,13 +7,12 @@ import ctypes
 import json
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+from child import run_graph_tool
 import photometric_cases as pc
 from manigaussian_amd import _lib, photometric
 
@@ -233,9 +232,7 @@ def test_render_photometric_loss_backward_captured_into_a_hip_graph_follows_targ
     """tests/tools/photometric_graph_capture_check.py in a process of its own (stream capture is process-wide state): render ->
     photometric_loss -> backward captured with torch.cuda.graph, replayed after the target images and the device-side weights
     were overwritten in place; the replay equals the eager step on the new targets and weights."""
-    tool = os.path.join(os.path.dirname(__file__), "tools", "photometric_graph_capture_check.py")
-    r = subprocess.run([sys.executable, tool], capture_output=True, text=True, timeout=170)
-    assert r.returncode == 0 and "GRAPH_OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    run_graph_tool("photometric_graph_capture_check.py", limit=170)
 
 
 # ---- without a GPU --------------------------------------------------------------------------------------------------------

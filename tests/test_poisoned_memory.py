@@ -103,6 +103,7 @@ import spatial_softmax_cases as ssc
 import volume_cases as vc
 import voxelize_cases as vz
 from manigaussian_amd import _lib, _ops
+from numerics import bits, same_bits
 
 gpu = pytest.mark.gpu
 ROOT = cf.ROOT
@@ -198,18 +199,6 @@ def test_the_two_bytes_read_back_as_the_issue_says():
 
 
 # ---- comparing --------------------------------------------------------------------------------------------------------------------
-_INTS = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
-
-
-def _as_ints(t):
-    t = t.contiguous()
-    return t.view(_INTS[t.element_size()]).reshape(-1)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and bool((_as_ints(a) == _as_ints(b)).all())
-
-
 def differences(tag, got, want, also=same_bits):
     """[] or [what is wrong with `got` against the clean `want` (CPU tensors, or None: not asked for)]; prints the count of differing
     elements, the largest difference, the newly non-finite ones and the first differing flat indices before anyone asserts."""
@@ -217,7 +206,7 @@ def differences(tag, got, want, also=same_bits):
         return [] if got is None and want is None else [(tag, "None on one side only")]
     if got.shape != want.shape or got.dtype != want.dtype:
         return [(tag, tuple(got.shape), got.dtype, "clean:", tuple(want.shape), want.dtype)]
-    wrong = _as_ints(got) != _as_ints(want)
+    wrong = bits(got) != bits(want)
     n = int(wrong.sum())
     worse, largest = 0, 0.0
     if got.numel():
@@ -227,8 +216,6 @@ def differences(tag, got, want, also=same_bits):
     where = wrong.nonzero().reshape(-1)[:8].tolist()
     print(f"{tag}: {n} of {got.numel()} elements differ, largest difference {largest:.3e}, {worse} newly non-finite" +
           (f", first at flat indices {where}" if n else ""))
-    if got.dtype != torch.float32 or got.dim() == 0:   # (the cases modules' same_bits take float32 tensors of at least one dimension)
-        also = same_bits
     return [(tag, n, largest, worse, where)] if (n or worse or not also(got, want)) else []
 
 
@@ -285,7 +272,7 @@ def test_control_what_is_not_written_stays_poison(byte, monkeypatch):
     else:
         assert t[3].item() == FLOAT_7F and (u == t[3]).all()
     assert ws is plain and again is plain and ws.dtype == torch.uint8 and ws.numel() == 4096 and bool((ws == byte).all())
-    assert not permuted.is_contiguous() and bool((_as_ints(permuted.cpu()).view(torch.uint8) == byte).all())
+    assert not permuted.is_contiguous() and bool((bits(permuted.cpu()).view(torch.uint8) == byte).all())
     assert e.numel() == 0 and h.device.type == "cpu"
     assert (torch.empty, torch.empty_like, _ops.workspace) == real
 

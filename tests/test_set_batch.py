@@ -7,6 +7,7 @@ import torch
 from manigaussian_amd import GaussianRasterizationSettings, GaussianRasterizer, GaussianRasterizerBatch, _lib
 from manigaussian_amd import synthetic as syn
 
+from child import run_graph_tool
 import util
 
 GRAD_TOL = 2e-5
@@ -351,12 +352,7 @@ def test_set_batch_workspaces_are_not_overrun(P, monkeypatch):
 def test_set_batch_captured_into_a_hip_graph_replays_bit_identically():
     """A set batch's forward + backward (async mode, two eager steps first) captured with torch.cuda.graph, in a process of
     its own (tests/tools/set_graph_capture_check.py): replays equal the eager step, images bit for bit."""
-    import os
-    import subprocess
-    import sys
-    tool = os.path.join(os.path.dirname(__file__), "tools", "set_graph_capture_check.py")
-    r = subprocess.run([sys.executable, tool], capture_output=True, text=True, timeout=170)
-    assert r.returncode == 0 and "GRAPH_OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    run_graph_tool("set_graph_capture_check.py", limit=170)
 
 
 @pytest.mark.gpu

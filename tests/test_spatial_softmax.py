@@ -10,13 +10,13 @@ On the GPU machine the reference does not exist: the full-size tests take the sa
 (spatial_softmax_cases.restatement, pinned against the fixtures here) in float64 as the truth and in float32 as the yardstick.
 """
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+from child import run_graph_tool
+from numerics import dev
 import spatial_softmax_cases as sc
 
 gpu = pytest.mark.gpu
@@ -183,10 +183,6 @@ def test_a_reference_shaped_state_dict_loads_strict():
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------------
-def dev():
-    return torch.device("cuda:0")
-
-
 def run(x, g_k, g_m, slices=0, module=None):
     """(keypoints, maxpool, dx) on the CPU: through the module (forward_with_max, or forward alone when g_m is None) or, with a
     forced split, through the private function underneath."""
@@ -353,6 +349,4 @@ def test_nothing_of_the_volumes_size_is_held():
 @gpu
 def test_forward_and_backward_captured_into_a_hip_graph():
     """In a child process: stream capture is process-wide state (tests/tools/spatial_softmax_graph_capture_check.py)."""
-    tool = os.path.join(ROOT, "tests", "tools", "spatial_softmax_graph_capture_check.py")
-    r = subprocess.run(["timeout", "-k", "10", "150", sys.executable, tool], capture_output=True, text=True, timeout=170)
-    assert r.returncode == 0 and "GRAPH_OK" in r.stdout, f"exit {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
+    run_graph_tool("spatial_softmax_graph_capture_check.py")

@@ -13,14 +13,14 @@ convolution between the fused pieces is MIOpen's.
 """
 import ctypes
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+from child import run_graph_tool
+from numerics import dev
 import volume_cases as vc
 
 gpu = pytest.mark.gpu
@@ -266,10 +266,6 @@ def test_the_workspace_size_is_positive_and_monotone():
 
 
 # ---- GPU -----------------------------------------------------------------------------------------------------------------------
-def dev():
-    return torch.device("cuda:0")
-
-
 def run(sources, upstream, s, p):
     """(out, [source gradients]) of the fused op on the device; the sources are used as they are (views stay views)."""
     from manigaussian_amd import resample_pad
@@ -382,6 +378,4 @@ def test_module_fixtures_on_the_device(name):
 @gpu
 def test_forward_and_backward_captured_into_a_hip_graph():
     """In a child process: stream capture is process-wide state (tests/tools/volume_graph_capture_check.py)."""
-    tool = os.path.join(ROOT, "tests", "tools", "volume_graph_capture_check.py")
-    r = subprocess.run(["timeout", "-k", "10", "150", sys.executable, tool], capture_output=True, text=True, timeout=170)
-    assert r.returncode == 0 and "GRAPH_OK" in r.stdout, f"exit {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
+    run_graph_tool("volume_graph_capture_check.py")

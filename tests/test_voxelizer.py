@@ -7,12 +7,11 @@ committed fixtures (tests/golden/voxelize/, what the reference gave where it exi
 against every fixture bit for bit on the CPU) stand in.
 """
 import os
-import subprocess
-import sys
 
 import pytest
 import torch
 
+from child import run_graph_tool
 import voxelize_cases as vc
 
 gpu = pytest.mark.gpu
@@ -256,7 +255,4 @@ def test_the_output_is_detached_and_a_side_stream_works():
 @gpu
 def test_voxelize_then_point_latent_captured_into_a_hip_graph():
     """In a child process: stream capture is process-wide state (tests/tools/voxelize_graph_capture_check.py)."""
-    tool = os.path.join(ROOT, "tests", "tools", "voxelize_graph_capture_check.py")
-    r = subprocess.run(["timeout", "-k", "10", "150", sys.executable, tool], capture_output=True, text=True, timeout=170)
-    print(r.stdout[-3000:], r.stderr[-3000:])
-    assert r.returncode == 0 and "GRAPH_OK" in r.stdout
+    run_graph_tool("voxelize_graph_capture_check.py")

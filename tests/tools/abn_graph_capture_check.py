@@ -6,25 +6,14 @@ runs, then replayed twice.  The kernels are deterministic, so after the k-th rep
 num_batches_tracked equal, bit for bit, the k-th of two eager calls that started from the same buffers: the running buffers and the
 counter advance once per replay, by the launch itself.  An aligned cube (rows split into several sub-slices) and an odd, batched
 volume (scalar heads and tails).  The queue settings stay the machine's defaults.  Prints GRAPH_OK on success."""
-import faulthandler
-import os
-import sys
+import _graph
+import torch
 
-faulthandler.enable()
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import torch  # noqa: E402
+import abn_cases as ac
+from manigaussian_amd import batch_norm_act
 
-import abn_cases as ac  # noqa: E402
-from manigaussian_amd import batch_norm_act  # noqa: E402
-
-dev = torch.device("cuda:0")
-
-
-def stage(msg):
-    print("stage:", msg, flush=True)
-
+dev = _graph.DEV
+NAMES = ("y", "dx", "dweight", "dbias", "running_mean", "running_var", "num_batches_tracked")
 
 for shape in ((1, 8, 40, 40, 40), (2, 3, 21, 19, 23)):
     C = shape[1]
@@ -50,15 +39,8 @@ for shape in ((1, 8, 40, 40, 40), (2, 3, 21, 19, 23)):
     def snapshot(y):
         return [t.detach().clone() for t in (y, x.grad, w.grad, b.grad, rm, rv, nbt)]
 
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        for _ in range(2):
-            reset()
-            step()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    stage(f"{shape}: warm-up done")
+    _graph.warm_up(step, before_each=reset)
+    _graph.stage(f"{shape}: warm-up done")
 
     reset()
     eager = []
@@ -70,18 +52,11 @@ for shape in ((1, 8, 40, 40, 40), (2, 3, 21, 19, 23)):
     assert not torch.equal(eager[0][4], eager[1][4]), "the running mean did not move between two eager steps"
 
     reset()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        out_y = step()
-    torch.cuda.synchronize()
+    graph, out_y = _graph.capture(step)
     assert int(nbt) == 0 and not bool(rm.any()), "the capture itself ran the kernels"
-    stage(f"{shape}: captured")
-    for k in range(2):
-        graph.replay()
-        torch.cuda.synchronize()
-        got = snapshot(out_y)   # (x.grad, w.grad, b.grad were None at capture: the backward's own output tensors)
-        for name, p, q in zip(("y", "dx", "dweight", "dbias", "running_mean", "running_var"), got, eager[k]):
-            assert ac.same_bits(p.cpu(), q.cpu()), f"{shape} replay {k + 1}: {name} differs from the eager call"
-        assert int(got[6]) == k + 1, f"{shape} replay {k + 1}: num_batches_tracked = {int(got[6])}"
-    stage(f"{shape}: two replays equal two eager calls bit for bit; the buffers advanced once per replay")
-print("GRAPH_OK")
+    _graph.stage(f"{shape}: captured")
+    # (x.grad, w.grad, b.grad were None at capture: the backward's own output tensors; no NaN fill: the running buffers and the
+    #  counter are read before they are written.  num_batches_tracked after replay k is the k-th eager call's: k, asserted above)
+    _graph.replays_equal(graph, lambda: snapshot(out_y), lambda k: eager[k - 1], NAMES, shape, poison=False)
+    _graph.stage(f"{shape}: two replays equal two eager calls bit for bit; the buffers advanced once per replay")
+_graph.ok()

@@ -7,27 +7,15 @@ device buffer and the captured in-place add advances the offset, so every replay
 differ, the offsets the replays saw are consecutive, and each replay's output and gradients equal, bit for bit, the eager
 kernels run on the state that replay saw -- and, within rounding, plain torch ops with that replay's keep mask
 (mgs_attention_dropout_mask).  The queue settings stay the machine's defaults.  Prints GRAPH_OK on success."""
-import faulthandler
-import os
-import sys
+import _graph
+import torch
 
-faulthandler.enable()
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import torch  # noqa: E402
+import attention_cases as ac
+from manigaussian_amd import Attention
+from manigaussian_amd.attention import dropout_keep_mask, fused_attention_kv
 
-import attention_cases as ac  # noqa: E402
-from manigaussian_amd import Attention  # noqa: E402
-from manigaussian_amd.attention import dropout_keep_mask, fused_attention_kv  # noqa: E402
-
-dev = torch.device("cuda:0")
+dev = _graph.DEV
 B, H, Nq, Nk, P = 2, 2, 150, 200, 0.1
-
-
-def stage(msg):
-    print("stage:", msg, flush=True)
-
 
 torch.manual_seed(3)
 m = Attention(16, context_dim=24, heads=H, dropout=P).to(dev).train()
@@ -44,27 +32,19 @@ def step():
     return out
 
 
-side = torch.cuda.Stream()
-side.wait_stream(torch.cuda.current_stream())
-with torch.cuda.stream(side):
-    for _ in range(2):
-        step()
-torch.cuda.current_stream().wait_stream(side)
-torch.cuda.synchronize()
-stage("warm-up done")
+_graph.warm_up(step)
+_graph.stage("warm-up done")
 for t in leaves:
     t.grad = None
-graph = torch.cuda.CUDAGraph()
-with torch.cuda.graph(graph):
-    out = step()
-stage("captured")
+graph, out = _graph.capture(step)
+_graph.stage("captured")
 seen = []
 for r in range(3):
     state = m.rng_state.clone()
     graph.replay()
     seen.append((state, out.detach().clone(), [t.grad.clone() for t in leaves]))
 torch.cuda.synchronize()
-stage("three replays, one synchronise")
+_graph.stage("three replays, one synchronise")
 
 for r, (state, got, grads) in enumerate(seen):
     assert int(state[1]) == 0xFFFFFFFE + 2 + r, (r, state.tolist())  # two warm-up runs, then one per replay
@@ -74,9 +54,7 @@ for r, (state, got, grads) in enumerate(seen):
     for t in leaves:
         t.grad = None
     eager.backward(g)
-    assert ac.same_bits(eager.detach().cpu(), got.cpu()), f"replay {r}: output differs from the eager call"
-    for t, a in zip(leaves, grads):
-        assert ac.same_bits(t.grad.cpu(), a.cpu()), f"replay {r}: a gradient differs from the eager call"
+    _graph.equal_bits([got] + grads, [eager] + [t.grad for t in leaves], ["the output"] + ["a gradient"] * len(leaves), f"replay {r}")
     # plain torch ops with this replay's keep mask
     keep = dropout_keep_mask(B, H, Nq, Nk, P, state)
     assert int((keep.cpu().numpy().astype(bool) != ac.keep_mask(int(state[0]), int(state[1]), B * H, Nq, Nk, P)).sum()) == 0
@@ -91,5 +69,5 @@ for r, (state, got, grads) in enumerate(seen):
         assert not ac.same_bits(got.cpu(), seen[r - 1][1].cpu()), "two consecutive replays drew the same mask"
         d = (got - seen[r - 1][1]).abs().max().item()
         assert d > 1e-3 * got.abs().max().item(), d
-stage("every replay equals the eager call on its own state and differs from its predecessor")
-print("GRAPH_OK")
+_graph.stage("every replay equals the eager call on its own state and differs from its predecessor")
+_graph.ok()

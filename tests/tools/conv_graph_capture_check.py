@@ -1,39 +1,31 @@
 """Run in its OWN process by test_forward_and_backward_captured_into_a_hip_graph of tests/test_conv3d.py, test_pointwise.py,
-test_narrow_conv.py and test_dense_conv.py (stream capture is process-wide state; a capture that goes wrong takes the process with
-it, not the test session):  conv_graph_capture_check.py <family>, a name of tests/conv_family.py's FAMILIES.
+test_narrow_conv.py, test_dense_conv.py and test_patch_conv.py (stream capture is process-wide state; a capture that goes wrong takes
+the process with it, not the test session):  conv_graph_capture_check.py <family> [<case> ...], a name of tests/conv_family.py's
+FAMILIES and names of that family's cases (none: the family's graph_cases).
 
 One forward + backward of the family's public op at each of its two graph cases (conv_family's graph_cases: conv3d `stem_in` and the
 transposed `up_op1`; pointwise `stem_out_batch`, single-word accesses and the fused backward, and `in_pre`, 16-byte accesses and the
 16-channel forms; narrow `odd`, word-by-word rows, three output channels and a batch, and `head`, the site's channels; dense
-`odd_k3`, a batch, odd rows, a partial N-tile and leaky ReLU, and `up0_last_head`, a site's channels at k = 5), each captured into ONE
-graph on a single stream after two eager warm-up runs, then replayed twice.  The kernels are deterministic and keep no state, so
-after every replay y, dx, dw and db equal the eager call's bit for bit.  The queue settings stay the machine's defaults.  Prints
-GRAPH_OK on success."""
-import faulthandler
-import os
+`odd_k3`, a batch, odd rows, a partial N-tile and leaky ReLU, and `up0_last_head`, a site's channels at k = 5; patch `odd`, a batch,
+rows off 16-byte boundaries, a partial N-tile and leaky ReLU, and `site_small`, the site's channels at k = 5 with uncovered voxels),
+each captured into ONE graph on a single stream after two eager warm-up runs, then replayed twice.  The kernels are deterministic and
+keep no state, so after every replay y, dx, dw and db equal the eager call's bit for bit.  The queue settings stay the machine's
+defaults.  Prints GRAPH_OK on success."""
 import sys
 
-faulthandler.enable()
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import torch  # noqa: E402
+import _graph
+import torch
 
-import conv_family as cf  # noqa: E402
+import conv_family as cf
 
 family = cf.FAMILIES[sys.argv[1]]
-dev = torch.device("cuda:0")
+cases = sys.argv[2:] or family.graph_cases
 
-
-def stage(msg):
-    print("stage:", msg, flush=True)
-
-
-for case in family.graph_cases:
+for case in cases:
     t = family.cases.make_inputs(case)
     names = [k for k in ("x", "w", "b") if t.get(k) is not None]
-    leaves = {k: t[k].to(dev).requires_grad_(True) for k in names}
-    g = t["g"].to(dev)
+    leaves = {k: t[k].to(_graph.DEV).requires_grad_(True) for k in names}
+    g = t["g"].to(_graph.DEV)
 
     def no_grads():
         for v in leaves.values():
@@ -48,29 +40,13 @@ for case in family.graph_cases:
     def results(y):
         return [y] + [v.grad for v in leaves.values()]
 
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        for _ in range(2):
-            step()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    stage(f"{case}: warm-up done")
-
-    eager = [v.detach().clone() for v in results(step())]
+    _graph.warm_up(step)
+    _graph.stage(f"{case}: warm-up done")
+    eager = _graph.copies(results(step()))
     torch.cuda.synchronize()
     no_grads()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        out_y = step()
-    torch.cuda.synchronize()
-    stage(f"{case}: captured")
-    for k in range(2):
-        for v in results(out_y):
-            v.detach().fill_(float("nan"))   # (a replay that wrote nothing would be seen)
-        graph.replay()
-        torch.cuda.synchronize()
-        for name, p, q in zip(["y"] + ["d" + n for n in names], results(out_y), eager):
-            assert cf.same_bits(p.detach().cpu(), q.cpu()), f"{case} replay {k + 1}: {name} differs from the eager call"
-    stage(f"{case}: two replays equal the eager call bit for bit")
-print("GRAPH_OK")
+    graph, out_y = _graph.capture(step)
+    _graph.stage(f"{case}: captured")
+    _graph.replays_equal(graph, lambda: results(out_y), eager, ["y"] + ["d" + n for n in names], case)
+    _graph.stage(f"{case}: two replays equal the eager call bit for bit")
+_graph.ok()

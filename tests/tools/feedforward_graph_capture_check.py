@@ -8,26 +8,16 @@ algorithms in the warm-up, so after every replay the output, the input's gradien
 bit, an eager call on the same inputs.  Inside the capture the library is entered exactly four times and no workspace is
 allocated (the warm-up's are reused: asserted); a host read of device memory or an allocation inside the library would end the
 capture with an error, which fails this script.  The queue settings stay the machine's defaults.  Prints GRAPH_OK on success."""
-import faulthandler
-import os
-import sys
+import _graph
+import torch
 
-faulthandler.enable()
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import torch  # noqa: E402
+import feedforward_cases as fc
+import manigaussian_amd
+from manigaussian_amd import _lib, _ops, feedforward
+from numerics import spy
 
-import feedforward_cases as fc  # noqa: E402
-import manigaussian_amd  # noqa: E402
-from manigaussian_amd import _lib, _ops, feedforward  # noqa: E402
-
-dev = torch.device("cuda:0")
+dev = _graph.DEV
 feedforward.ROUTE.update(layer_norm=True, bias_geglu=True)
-
-
-def stage(msg):
-    print("stage:", msg, flush=True)
 
 
 def inputs(seed):
@@ -46,10 +36,8 @@ params = dict(m.named_parameters())
 x, g = (t.to(dev) for t in inputs(60))
 x.requires_grad_(True)
 
-launches = {}
-for name in ("mgs_layernorm_forward", "mgs_layernorm_backward", "mgs_bias_geglu_forward", "mgs_bias_geglu_backward"):
-    real = getattr(_lib.lib(), name)
-    setattr(_lib.lib(), name, (lambda *a, _r=real, _n=name: (launches.__setitem__(_n, launches.get(_n, 0) + 1), _r(*a))[1]))
+FUSED = ("mgs_layernorm_forward", "mgs_layernorm_backward", "mgs_bias_geglu_forward", "mgs_bias_geglu_backward")
+launches = spy(_lib.lib(), FUSED)
 
 
 def step():
@@ -63,39 +51,28 @@ def clear():
     m.zero_grad(set_to_none=True)
 
 
-side = torch.cuda.Stream()
-side.wait_stream(torch.cuda.current_stream())
-with torch.cuda.stream(side):
-    for _ in range(2):
-        step()
-torch.cuda.current_stream().wait_stream(side)
-torch.cuda.synchronize()
-stage("warm-up done")
+_graph.warm_up(step)
+_graph.stage("warm-up done")
 clear()
 launches.clear()
 workspaces = dict(_ops._WORKSPACES)
-graph = torch.cuda.CUDAGraph()
-with torch.cuda.graph(graph):
-    out_graph = step()
+graph, out_graph = _graph.capture(step)
 grads_graph = {"x": x.grad, **{k: v.grad for k, v in params.items()}}  # written in place by every replay
-assert launches == {"mgs_layernorm_forward": 1, "mgs_layernorm_backward": 1, "mgs_bias_geglu_forward": 1,
-                    "mgs_bias_geglu_backward": 1}, launches
+assert {k: len(v) for k, v in launches.items()} == dict.fromkeys(FUSED, 1), launches
 assert dict(_ops._WORKSPACES) == workspaces, "the capture took no new workspace: the warm-up's are reused"
-stage("captured: the four fused calls, no new workspace")
+_graph.stage("captured: the four fused calls, no new workspace")
 for seed in (61, 62):
     new = inputs(seed)
     with torch.no_grad():
         x.copy_(new[0].to(dev))
         g.copy_(new[1].to(dev))
-    graph.replay()
-    torch.cuda.synchronize()
+    _graph.replay(graph)
     got = {"out": out_graph.detach().clone(), **{k: v.clone() for k, v in grads_graph.items()}}
     clear()
     out = step()
     torch.cuda.synchronize()
     eager = {"out": out.detach(), "x": x.grad, **{k: v.grad for k, v in params.items()}}
-    for k in got:
-        assert fc.same_bits(got[k].cpu(), eager[k].cpu()), f"seed {seed}: the replayed {k} differs from the eager call"
+    _graph.equal_bits(got.values(), [eager[k] for k in got], [f"the replayed {k}" for k in got], f"seed {seed}")
     # the same block in float64 on the CPU, where the drop-ins take torch's own composition
     want_m = manigaussian_amd.PreNorm(64, manigaussian_amd.FeedForward(64))
     want_m.load_state_dict({k: v.detach().cpu() for k, v in m.state_dict().items()}, strict=True)
@@ -107,5 +84,5 @@ for seed in (61, 62):
     x.grad = grads_graph["x"]
     for k, v in params.items():
         v.grad = grads_graph[k]
-    stage(f"seed {seed}: the replay equals the eager call bit for bit")
-print("GRAPH_OK")
+    _graph.stage(f"seed {seed}: the replay equals the eager call bit for bit")
+_graph.ok()

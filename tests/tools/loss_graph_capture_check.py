@@ -6,34 +6,19 @@ with DEVICE-side weights -> backward -- captured with torch.cuda.graph after eag
 graph is replayed after the target images and the weights were overwritten in place; the replay must equal the eager step on
 the new targets and weights: loss and terms bit for bit (the loss kernels are deterministic and the images are), parameter
 gradients to float-atomic order (the rasterizer backward).  Prints GRAPH_OK on success."""
-import faulthandler
-import os
-import sys
+import _graph
+import torch
 
-faulthandler.enable()
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import torch  # noqa: E402
-
-import manigaussian_amd as mg  # noqa: E402
+import manigaussian_amd as mg
 
 mg.set_forward_mode("async")  # graph capture needs forwards that never synchronise
-from manigaussian_amd import synthetic as syn  # noqa: E402
-from manigaussian_amd.gaussian_renderer import render_sets_stacked  # noqa: E402
+from manigaussian_amd import synthetic as syn
+from manigaussian_amd.gaussian_renderer import render_sets_stacked
 
-dev = torch.device("cuda:0")
+dev = _graph.DEV
 P, F, W = 16384, 3, 128
 sc = syn.make_scene(P, F=F, M=4, seed=5)
 cams = syn.circle_cameras(4, W, W, negative_focal=True)
-
-
-def data_of(cam):
-    # host copies of the camera scalars (what manigaussian_amd.camera.TargetCache hands out): no device read per render
-    kw = syn.camera_settings_kwargs(cam, 1, True, device=dev)
-    return {"novel_view": {"tanfov_host": [(kw["tanfovx"], kw["tanfovy"])], "size_host": [(W, W)],
-                           "world_view_transform": kw["viewmatrix"][None], "full_proj_transform": kw["projmatrix"][None],
-                           "camera_center": kw["campos"][None]}}
 
 
 g = torch.Generator().manual_seed(6)
@@ -44,7 +29,7 @@ new_rgb, new_embed = torch.rand(2, W, W, 3, generator=g).to(dev), torch.randn(1,
 weights = torch.tensor([[1.0, 0.01], [0.0, 0.0]]).to(dev)  # before the warm-up: lambda_dyna = 0
 new_weights = torch.tensor([[1.0, 0.01], [0.01, 0.0]]).to(dev)
 leaves = {k: v.to(dev).clone().requires_grad_(True) for k, v in sc.items()}
-datas = [data_of(cams[0]), data_of(cams[2])]
+datas = [_graph.data_of(cams[0], W, dev), _graph.data_of(cams[2], W, dev)]
 bg = torch.zeros(3, device=dev)
 
 
@@ -60,54 +45,17 @@ def step():
     return (loss, d["loss_rgb"], d["loss_embed"], d["loss_dyna"], d["psnr"], batch["render"], batch["render_embed"]) + grads
 
 
-def stage(msg):
-    print("stage:", msg, flush=True)
-
-
 NV = 7  # values that must replay bit for bit; the rest are parameter gradients
-for _ in range(3):
-    eager = [t.detach().clone() for t in step()]
-    mg.check_status(dev)
-stage("eager steps done")
-side = torch.cuda.Stream()
-side.wait_stream(torch.cuda.current_stream())
-with torch.cuda.stream(side):
-    step()
-torch.cuda.current_stream().wait_stream(side)
-torch.cuda.synchronize()
-stage("side-stream warm-up done")
-graph = torch.cuda.CUDAGraph()
-with torch.cuda.graph(graph):
-    out = step()
-stage("captured")
-for _ in range(3):
-    graph.replay()
-torch.cuda.synchronize()
+graph, out, eager = _graph.captured_step(step, dev, eager=3, replays=3)
 mg.check_status(dev)
-stage("replayed")
-
-
-def same(got, want, what):
-    for i, (a, b) in enumerate(zip(got[:NV], want[:NV])):
-        assert torch.equal(a, b), f"{what}: value {i} differs"
-    for a, b in zip(got[NV:], want[NV:]):
-        assert (a - b).abs().max().item() <= 2e-5 * b.abs().max().item() + 1e-12, f"{what}: gradients differ"
-
-
-same(out, eager, "replay vs eager")
-stage("replays equal the eager step")
+_graph.stage("replayed")
+_graph.same_step(out, eager, NV, "replay vs eager")
+_graph.stage("replays equal the eager step")
 with torch.no_grad():  # new targets and the warm-up's end, in place: the graph reads them where they live
     gt_rgb.copy_(new_rgb)
     gt_embed.copy_(new_embed)
     weights.copy_(new_weights)
-torch.cuda.synchronize()
-graph.replay()
-torch.cuda.synchronize()
-replayed = [t.detach().clone() for t in out]
-moved = [t.detach().clone() for t in step()]
-torch.cuda.synchronize()
-mg.check_status(dev)
-same(replayed, moved, "replay vs eager on the new targets and weights")
+moved = _graph.replay_follows(graph, out, step, dev, NV, "replay vs eager on the new targets and weights")
 assert not torch.equal(moved[0], eager[0]) and eager[3].item() > 0
 assert moved[NV].shape == leaves["means3D"].shape
-print("GRAPH_OK")
+_graph.ok()

@@ -15,33 +15,19 @@ into ONE graph after eager warm-up steps, then replayed while the learning rate 
      L2 share of 1e-2 allows one element in 10 000 to do so);
   3. the learning rate is followed: a replay at lr = 0 leaves the parameters bit for bit where they were.
 Prints GRAPH_OK on success."""
-import faulthandler
-import os
-import sys
+import _graph
+import torch
 
-faulthandler.enable()
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import torch  # noqa: E402
-
-import manigaussian_amd as mg  # noqa: E402
+import manigaussian_amd as mg
 
 mg.set_forward_mode("async")  # graph capture needs forwards that never synchronise
-from manigaussian_amd import synthetic as syn  # noqa: E402
-from manigaussian_amd.gaussian_renderer import render_sets_stacked  # noqa: E402
+from manigaussian_amd import synthetic as syn
+from manigaussian_amd.gaussian_renderer import render_sets_stacked
 
-dev = torch.device("cuda:0")
+dev = _graph.DEV
 P, F, W = 16384, 3, 128
 sc = syn.make_scene(P, F=F, M=4, seed=5)
 cams = syn.circle_cameras(4, W, W, negative_focal=True)
-
-
-def data_of(cam):
-    kw = syn.camera_settings_kwargs(cam, 1, True, device=dev)
-    return {"novel_view": {"tanfov_host": [(kw["tanfovx"], kw["tanfovy"])], "size_host": [(W, W)],
-                           "world_view_transform": kw["viewmatrix"][None], "full_proj_transform": kw["projmatrix"][None],
-                           "camera_center": kw["campos"][None]}}
 
 
 g = torch.Generator().manual_seed(6)
@@ -49,15 +35,11 @@ dxyz, drot = (0.01 * torch.randn(P, 3, generator=g)).to(dev), (0.05 * torch.rand
 gt_rgb = torch.rand(2, W, W, 3, generator=g).to(dev)
 gt_embed = torch.randn(1, F, W, W, generator=g).to(dev)
 weights = torch.tensor([[1.0, 0.01], [0.01, 0.0]]).to(dev)
-datas = [data_of(cams[0]), data_of(cams[2])]
+datas = [_graph.data_of(cams[0], W, dev), _graph.data_of(cams[2], W, dev)]
 bg = torch.zeros(3, device=dev)
 HYPER = dict(betas=(0.9, 0.999), eps=1e-6, weight_decay=1e-6)
 LRS = [5e-4, 5e-4, 2.5e-4, 1e-3, 1e-4]  # the schedule: one value per step
 WARM = 2
-
-
-def stage(msg):
-    print("stage:", msg, flush=True)
 
 
 class Trainer:
@@ -99,7 +81,7 @@ for lr in LRS:
     eager_params.append(eager.params())
 torch.cuda.synchronize()
 assert not eager.flat.any().item(), "zero_grad=True left gradients behind"
-stage("eager trajectory done")
+_graph.stage("eager trajectory done")
 
 # ---- the captured one: WARM eager steps, then one graph replayed for the rest ------------------------------------------------
 tr = Trainer(start)
@@ -127,35 +109,27 @@ for lr in LRS[:WARM]:
     losses.append(tr.step().clone())
     mg.check_status(dev)
     shadow_step(lr)
-stage("warm-up steps done")
-side = torch.cuda.Stream()
-side.wait_stream(torch.cuda.current_stream())
+_graph.stage("warm-up steps done")
 saved = tr.params(), [t.clone() for t in (tr.opt._layout["state"],)]
-with torch.cuda.stream(side):
-    tr.lr.fill_(0.0)
-    tr.step()  # (lr = 0 moves no parameter, but the moments advance: put both back below)
-torch.cuda.current_stream().wait_stream(side)
-torch.cuda.synchronize()
+# (lr = 0, written on the side stream, moves no parameter, but the moments advance: put both back below)
+_graph.warm_up(tr.step, runs=1, before_each=lambda: tr.lr.fill_(0.0))
 with torch.no_grad():
     for p, q in zip(tr.leaves.values(), saved[0]):
         assert torch.equal(p.detach(), q), "a step at lr = 0 moved a parameter"
     tr.opt._layout["state"].copy_(saved[1][0])
-stage("side-stream warm-up done")
-graph = torch.cuda.CUDAGraph()
-with torch.cuda.graph(graph):
-    out_loss = tr.step()
-stage("captured")
+_graph.stage("side-stream warm-up done")
+graph, out_loss = _graph.capture(tr.step)
+_graph.stage("captured")
 with torch.no_grad():  # (capture executes nothing: state and parameters are as saved)
     for p, q in zip(tr.leaves.values(), saved[0]):
         assert torch.equal(p.detach(), q)
 for lr in LRS[WARM:]:
     tr.lr.fill_(lr)  # the schedule, written in place between replays
-    graph.replay()
-    torch.cuda.synchronize()
+    _graph.replay(graph)
     mg.check_status(dev)
     losses.append(out_loss.clone())
     shadow_step(lr)
-stage("replays equal the eager optimizer on the replays' gradients, bit for bit")
+_graph.stage("replays equal the eager optimizer on the replays' gradients, bit for bit")
 assert not tr.flat.any().item(), "zero_grad=True left gradients behind in the graph"
 
 # ---- 2. against the eager trajectory -----------------------------------------------------------------------------------------
@@ -169,13 +143,12 @@ for name, p, q, p0 in zip(start, tr.params(), eager_params[-1], first):
     diff = (p - q).double().norm().item()
     print(f"{name}: |graph - eager| {diff:.3g} of |eager - start| {moved:.3g} ({diff / moved if moved else 0:.3g})")
     assert moved > 0 and diff <= 1e-2 * moved, name
-stage("the replayed trajectory equals the eager one")
+_graph.stage("the replayed trajectory equals the eager one")
 
 # ---- 3. lr = 0 ------------------------------------------------------------------------------------------------------------------
 before = tr.params()
 tr.lr.fill_(0.0)
-graph.replay()
-torch.cuda.synchronize()
+_graph.replay(graph)
 for p, q in zip(tr.params(), before):
     assert torch.equal(p, q), "a replay at lr = 0 moved a parameter"
-print("GRAPH_OK")
+_graph.ok()

@@ -4,24 +4,17 @@
 The scene whose blocks are handed 16 chunks and visit 5 -- the render forward skips its second chunk slot -- forward + backward
 through the public autograd API, captured with torch.cuda.graph: the replay reproduces the eager images and radii bit for bit.
 Prints GRAPH_OK on success."""
-import faulthandler
-import os
-import sys
+import _graph
+import torch
 
-faulthandler.enable()
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import torch  # noqa: E402
-
-import manigaussian_amd as mg  # noqa: E402
+import manigaussian_amd as mg
 
 mg.set_forward_mode("async")  # graph capture needs forwards that never synchronise (opt-in; the default is "safe")
-import reachable_chunks_cases as rc  # noqa: E402
-from manigaussian_amd import GaussianRasterizationSettings, GaussianRasterizer  # noqa: E402
-from manigaussian_amd import synthetic as syn  # noqa: E402
+import reachable_chunks_cases as rc
+from manigaussian_amd import GaussianRasterizationSettings, GaussianRasterizer
+from manigaussian_amd import synthetic as syn
 
-dev = torch.device("cuda:0")
+dev = _graph.DEV
 F = 32
 sc, cam, kw, dC, dF = rc.stack_scene(n=1100, opacity=rc.die_after(300), F=F)
 m = rc.chunk_model(rc.oracle_forward(sc, kw)[3])
@@ -38,24 +31,7 @@ def step():
     return (c, f, r) + torch.autograd.grad([c, f], list(leaves.values()), [dC, dF])
 
 
-for _ in range(3):
-    # (detached copies: a kept output would keep its autograd graph alive into the capture)
-    eager = [t.detach().clone() for t in step()]
-    mg.check_status(dev)
-side = torch.cuda.Stream()
-side.wait_stream(torch.cuda.current_stream())
-with torch.cuda.stream(side):
-    step()  # warm-up on a side stream, as torch's capture recipe asks
-torch.cuda.current_stream().wait_stream(side)
-torch.cuda.synchronize()
-graph = torch.cuda.CUDAGraph()
-with torch.cuda.graph(graph):
-    out = step()
-for _ in range(2):
-    graph.replay()
-torch.cuda.synchronize()
+graph, out, eager = _graph.captured_step(step, dev, eager=3, replays=2)
 mg.check_status(dev)
-assert torch.equal(out[0], eager[0]) and torch.equal(out[1], eager[1]) and torch.equal(out[2], eager[2]), "images differ"
-for a, b in zip(out[3:], eager[3:]):
-    assert (a - b).abs().max().item() <= 2e-5 * b.abs().max().item() + 1e-12, "gradients differ"
-print("GRAPH_OK")
+_graph.same_step(out, eager, 3, "replay vs eager")
+_graph.ok()

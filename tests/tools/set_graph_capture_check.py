@@ -2,24 +2,17 @@
 (stream capture is process-wide state).  ManiGaussian's step shape as a set batch -- two sets of 16 384 Gaussians, one view
 each, F = 3 -- forward + backward captured with torch.cuda.graph after two eager steps; replays must reproduce the eager
 images bit for bit and the gradients to float-atomic order.  Prints GRAPH_OK on success."""
-import faulthandler
-import os
-import sys
+import _graph
+import torch
 
-faulthandler.enable()
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import torch  # noqa: E402
-
-import manigaussian_amd as mg  # noqa: E402
+import manigaussian_amd as mg
 
 mg.set_forward_mode("async")
-import util  # noqa: E402
-from manigaussian_amd import GaussianRasterizationSettings, GaussianRasterizerBatch  # noqa: E402
-from manigaussian_amd import synthetic as syn  # noqa: E402
+import util
+from manigaussian_amd import GaussianRasterizationSettings, GaussianRasterizerBatch
+from manigaussian_amd import synthetic as syn
 
-dev = torch.device("cuda:0")
+dev = _graph.DEV
 P, F, W = 16384, 3, 128
 scs = [util.scene_case(P=P, F=F, seed=2 + 7 * s)[0] for s in range(2)]
 leaves = {k: torch.stack([sc[k] for sc in scs]).to(dev).requires_grad_(True) for k in scs[0]}
@@ -38,24 +31,9 @@ def step():
     return (c, f, r) + torch.autograd.grad([c, f], list(leaves.values()), [dC, dF])
 
 
-for _ in range(2):
-    eager = [t.detach().clone() for t in step()]
-    mg.check_status(dev)
-side = torch.cuda.Stream()
-side.wait_stream(torch.cuda.current_stream())
-with torch.cuda.stream(side):
-    step()
-torch.cuda.current_stream().wait_stream(side)
-torch.cuda.synchronize()
-graph = torch.cuda.CUDAGraph()
-with torch.cuda.graph(graph):
-    out = step()
-for _ in range(3):
-    graph.replay()
-torch.cuda.synchronize()
+graph, out, eager = _graph.captured_step(step, dev, eager=2, replays=3)
 mg.check_status(dev)
-assert torch.equal(out[0], eager[0]) and torch.equal(out[1], eager[1]) and torch.equal(out[2], eager[2]), "images differ"
 for a, b in zip(out[3:], eager[3:]):
     assert a.shape == b.shape and a.shape[0] == 2
-    assert (a - b).abs().max().item() <= 2e-5 * b.abs().max().item() + 1e-12, "gradients differ"
-print("GRAPH_OK")
+_graph.same_step(out, eager, 3, "replay vs eager")
+_graph.ok()

@@ -6,25 +6,14 @@ volumes and upstream gradients are written IN PLACE into the tensors the graph r
 every replay keypoints, maxpool and the volume's gradient equal, bit for bit, an eager call on the same inputs, and lie within
 the fixture bounds' yardstick of the float64 restatement.  An aligned cube (rows split in several slices) and an odd, non-cube
 volume (scalar heads and tails).  The queue settings stay the machine's defaults.  Prints GRAPH_OK on success."""
-import faulthandler
-import os
-import sys
+import _graph
+import torch
 
-faulthandler.enable()
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import torch  # noqa: E402
+import spatial_softmax_cases as sc
+from manigaussian_amd import SpatialSoftmax3D
 
-import spatial_softmax_cases as sc  # noqa: E402
-from manigaussian_amd import SpatialSoftmax3D  # noqa: E402
-
-dev = torch.device("cuda:0")
+dev = _graph.DEV
 T = sc.TEMPERATURE
-
-
-def stage(msg):
-    print("stage:", msg, flush=True)
 
 
 def inputs(shape, seed):
@@ -44,34 +33,24 @@ for shape in ((1, 8, 40, 40, 40), (2, 3, 21, 19, 23)):
         ((kp * g_k).sum() + (mx * g_m).sum()).backward()
         return kp, mx
 
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        for _ in range(2):
-            step()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    stage(f"{shape}: warm-up done")
+    _graph.warm_up(step)
+    _graph.stage(f"{shape}: warm-up done")
     x.grad = None
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        out_kp, out_mx = step()
+    graph, (out_kp, out_mx) = _graph.capture(step)
     out_dx = x.grad  # written in place by every replay (x.grad was None at capture: the backward's own output tensor)
-    stage(f"{shape}: captured")
+    _graph.stage(f"{shape}: captured")
     for seed in (50, 51, 52, 53):
         new = inputs(shape, seed)
         with torch.no_grad():
             for dst, src in zip((x, g_k, g_m), new):
                 dst.copy_(src.to(dev))
-        graph.replay()
-        torch.cuda.synchronize()
+        _graph.replay(graph)
         got = (out_kp.detach().clone(), out_mx.detach().clone(), out_dx.clone())
         x.grad = None
         kp, mx = step()
         torch.cuda.synchronize()
         eager = (kp.detach(), mx.detach(), x.grad.clone())
-        for name, a, b in zip(("keypoints", "maxpool", "dx"), got, eager):
-            assert sc.same_bits(a.cpu(), b.cpu()), f"{shape} seed {seed}: the replayed {name} differs from the eager call"
+        _graph.equal_bits(got, eager, ("the replayed keypoints", "the replayed maxpool", "the replayed dx"), f"{shape} seed {seed}")
         xx = new[0].double().requires_grad_(True)
         kp64, mx64 = sc.restatement(xx, D, H, W, T, torch.float64)
         ((kp64 * new[1].double()).sum() + (mx64 * new[2].double()).sum()).backward()
@@ -79,5 +58,5 @@ for shape in ((1, 8, 40, 40, 40), (2, 3, 21, 19, 23)):
         e_dx = (got[2].cpu().double() - xx.grad).abs().max().item() / xx.grad.abs().max().item()
         print(f"{shape} seed {seed}: keypoints err {e_kp:.2e}, dx err {e_dx:.2e} of max|dx|")
         assert torch.equal(got[1].cpu().double(), mx64.detach()) and e_kp <= 1e-5 and e_dx <= 1e-4
-    stage(f"{shape}: replays equal the eager calls bit for bit")
-print("GRAPH_OK")
+    _graph.stage(f"{shape}: replays equal the eager calls bit for bit")
+_graph.ok()

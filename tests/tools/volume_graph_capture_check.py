@@ -6,25 +6,14 @@ replayed twice while a new input and a new upstream gradient are written IN PLAC
 op is deterministic, and MIOpen picks its convolution algorithms in the warm-up, so after every replay the output, the input's
 gradient and every parameter's gradient equal, bit for bit, an eager call on the same inputs.  The queue settings stay the
 machine's defaults.  Prints GRAPH_OK on success."""
-import faulthandler
-import os
-import sys
+import _graph
+import torch
 
-faulthandler.enable()
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import torch  # noqa: E402
+import volume_cases as vc
+import manigaussian_amd
 
-import volume_cases as vc  # noqa: E402
-import manigaussian_amd  # noqa: E402
-
-dev = torch.device("cuda:0")
+dev = _graph.DEV
 NAME = "up_s2_k3"
-
-
-def stage(msg):
-    print("stage:", msg, flush=True)
 
 
 def inputs(seed):
@@ -50,34 +39,24 @@ def clear():
     m.zero_grad(set_to_none=True)
 
 
-side = torch.cuda.Stream()
-side.wait_stream(torch.cuda.current_stream())
-with torch.cuda.stream(side):
-    for _ in range(2):
-        step()
-torch.cuda.current_stream().wait_stream(side)
-torch.cuda.synchronize()
-stage("warm-up done")
+_graph.warm_up(step)
+_graph.stage("warm-up done")
 clear()
-graph = torch.cuda.CUDAGraph()
-with torch.cuda.graph(graph):
-    out_graph = step()
+graph, out_graph = _graph.capture(step)
 grads_graph = {"x": x.grad, **{k: v.grad for k, v in params.items()}}  # written in place by every replay
-stage("captured")
+_graph.stage("captured")
 for seed in (61, 62):
     new = inputs(seed)
     with torch.no_grad():
         x.copy_(new[0].to(dev))
         g.copy_(new[1].to(dev))
-    graph.replay()
-    torch.cuda.synchronize()
+    _graph.replay(graph)
     got = {"out": out_graph.detach().clone(), **{k: v.clone() for k, v in grads_graph.items()}}
     clear()
     out = step()
     torch.cuda.synchronize()
     eager = {"out": out.detach(), "x": x.grad, **{k: v.grad for k, v in params.items()}}
-    for k in got:
-        assert vc.same_bits(got[k].cpu(), eager[k].cpu()), f"seed {seed}: the replayed {k} differs from the eager call"
+    _graph.equal_bits(got.values(), [eager[k] for k in got], [f"the replayed {k}" for k in got], f"seed {seed}")
     want = vc.run_module(vc.fixture_module(vc.plain, NAME), new[0], new[1], torch.float64)
     e_out, e_dx = vc.rel_err(got["out"].cpu(), want[0]), vc.rel_err(got["x"].cpu(), want[1])
     print(f"seed {seed}: out err {e_out:.2e}, dx err {e_dx:.2e} of the float64 layers on the CPU")
@@ -86,5 +65,5 @@ for seed in (61, 62):
     x.grad = grads_graph["x"]
     for k, v in params.items():
         v.grad = grads_graph[k]
-    stage(f"seed {seed}: the replay equals the eager call bit for bit")
-print("GRAPH_OK")
+    _graph.stage(f"seed {seed}: the replay equals the eager call bit for bit")
+_graph.ok()

@@ -6,26 +6,15 @@ into ONE graph after eager warm-up, then replayed while new clouds, colours and 
 the graph reads.  The voxelizer is deterministic, so after every replay the grid equals, bit for bit, both an eager call on the
 same inputs and the CPU restatement; the gathered latents equal the eager ones bit for bit as well (a gather adds nothing).
 Both memory layouts.  Prints GRAPH_OK on success."""
-import faulthandler
-import os
-import sys
+import _graph
+import torch
 
-faulthandler.enable()
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import torch  # noqa: E402
+import voxelize_cases as vc
+from manigaussian_amd import point_latent_pe
+from manigaussian_amd.voxelizer import voxelize
 
-import voxelize_cases as vc  # noqa: E402
-from manigaussian_amd import point_latent_pe  # noqa: E402
-from manigaussian_amd.voxelizer import voxelize  # noqa: E402
-
-dev = torch.device("cuda:0")
+dev = _graph.DEV
 B, N, V, P = 1, 16384, 100, 4096
-
-
-def stage(msg):
-    print("stage:", msg, flush=True)
 
 
 def inputs(seed):
@@ -46,24 +35,15 @@ for memory in ("channels_first", "channels_last"):
         vox = voxelize(coords, feats, bounds, V, memory)
         return vox, point_latent_pe(vox.permute(0, 4, 1, 2, 3), query, vc.SCENE_BOUNDS)
 
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        for _ in range(2):
-            step()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    stage(f"{memory}: warm-up done")
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        out_vox, out_lat = step()
-    stage(f"{memory}: captured")
+    _graph.warm_up(step)
+    _graph.stage(f"{memory}: warm-up done")
+    graph, (out_vox, out_lat) = _graph.capture(step)
+    _graph.stage(f"{memory}: captured")
     for seed in (100, 101, 102, 103):
         new = inputs(seed)
         for dst, src in zip((coords, feats, bounds), new):
             dst.copy_(src.to(dev))
-        graph.replay()
-        torch.cuda.synchronize()
+        _graph.replay(graph)
         got_vox, got_lat = out_vox.clone(), out_lat.clone()
         eager_vox, eager_lat = step()
         torch.cuda.synchronize()
@@ -71,7 +51,6 @@ for memory in ("channels_first", "channels_last"):
         n = int((vc.bits(got_vox.cpu()) != vc.bits(exp)).sum())
         print(f"{memory} seed {seed}: {n} floats of the replayed grid differ from the restatement, occupied {int(exp[..., -1].sum())}")
         assert n == 0
-        assert vc.same_bits(got_vox.cpu(), eager_vox.cpu()), "the replayed grid and the eager one differ"
-        assert vc.same_bits(got_lat.cpu(), eager_lat.cpu()), "the replayed latents and the eager ones differ"
-    stage(f"{memory}: replays equal the eager calls and the restatement, bit for bit")
-print("GRAPH_OK")
+        _graph.equal_bits((got_vox, got_lat), (eager_vox, eager_lat), ("the replayed grid", "the replayed latents"), f"{memory} seed {seed}")
+    _graph.stage(f"{memory}: replays equal the eager calls and the restatement, bit for bit")
+_graph.ok()

@@ -19,6 +19,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from numerics import rel_err, same_bits  # noqa: F401  (re-exported: the tests and the tools reach them through this module)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN_DIR = os.path.join(ROOT, "tests", "golden", "volume")
 REF_FILE = os.path.join(os.environ.get("MGS_REFERENCE_ROOT", "/root/reference"), "helpers", "network_utils.py")
@@ -104,13 +106,6 @@ def restatement(sources, scale, pad, dtype=torch.float64):
     return torch.einsum("zk,yj,xi,bckji->bczyx", Az, Ay, Ax, x)
 
 
-def rel_err(got, truth):
-    """max|got - truth| over max|truth| (0 for an all-zero truth that is met)."""
-    mag = truth.abs().max().item()
-    d = (got.double() - truth.double()).abs().max().item()
-    return d / mag if mag > 0 else d
-
-
 def bound(ref_err):
     """Largest allowed relative error for a tensor whose float32 reference has ref_err."""
     return FACTOR * max(ref_err, FLOOR)
@@ -131,10 +126,6 @@ def truth(case):
         assert max([errs["out"]] + errs["grads"]) <= REF_ERR_CEILING, (case, errs)
         _TRUTH[case] = dict(sources=sources, upstream=upstream, out64=out64, grads64=g64, ref_err=errs)
     return _TRUTH[case]
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and bool((a.contiguous().view(torch.int32) == b.contiguous().view(torch.int32)).all())
 
 
 # ---- the module fixtures ---------------------------------------------------------------------------------------------------------

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 import ref_import
+from numerics import bits, same_bits  # noqa: F401  (re-exported: the tests and the tools reach them through this module)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN_DIR = os.path.join(HERE, "golden", "voxelize")
@@ -176,14 +177,6 @@ def reference_run(coords, features, bounds, V):
 
 
 # ---- fixtures ------------------------------------------------------------------------------------------------------------------
-def bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
-
-
 def fixture_of_grid(case, coords, features, bounds, V, grid):
     Fc = 0 if features is None else features.shape[-1]
     occ = grid[..., -1] > 0

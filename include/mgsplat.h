@@ -943,6 +943,31 @@ int mgs_pointwise_forward(int64_t B, int Cin, int Cout, int64_t n, const float* 
 int mgs_pointwise_backward(int64_t B, int Cin, int Cout, int64_t n, const float* x, const float* g_y, const float* w, float* dx,
                            float* dw, float* db, void* workspace, size_t workspace_bytes, int split, mgs_stream_t stream);
 
+/* ---- the same pointwise convolution for 65..256 output channels (conv_out at final_dim = 128: nn.Conv3d(8, 128, 1, bias=True),
+ * conf/method/ManiGaussian_BC.yaml:35) -- additive exports, ABI v17 ----
+ * Kernel 1x1x1, stride 1, no padding, groups 1; Cin = 1..16 (what the fused backward holds per lane, so that g_y is read once),
+ * Cout = 65..256 (below 65 mgs_pointwise_* is the op); n = D H W.  Parameters, layouts, alignment, formulas and error codes are those
+ * of mgs_pointwise_* above.
+ * The forward and the input gradient alone are mgs_pointwise_*'s own kernels, one launch each.  With dw or db a workgroup walks its
+ * run of tiles once per BLOCK of 64 output channels, in ascending order: in block c wave k owns channels 64 c + 8 k .. + 7 and
+ * writes those rows of the run's one RECORD [Cout, Cin + 1]; g_y is read once, x once per block; where dx is asked for it is written
+ * once per block, and in a block after the first every element's sum starts from what the same thread stored for it in the block
+ * before.  That makes dx one chain over the groups of 8 output channels in ascending order, the order of the launch that computes dx
+ * alone: dx is the same bits whether or not dw and db are asked for.  Records, merge launch and split as above: dw and db are the
+ * same bits for every split.
+ * workspace: 16-byte aligned, at least as many bytes as the size query returns for the same shape (0 for sizes outside the limits,
+ * else a multiple of 256).
+ * MGS_ERR_INVALID_ARG before any launch: Cin outside 1..16; Cout outside 65..256; B or n below 1; n >= 2^31, or B times the number
+ * of tiles above 2^31 - 1; a NULL pointer where one is required (dx, dw and db all NULL included); a pointer not 16-byte aligned;
+ * split outside [0, 64].  MGS_ERR_WORKSPACE: fewer bytes than the query's.  Element offsets are 64-bit.
+ * No atomics, no workgroup waits for another, nothing to zero: bit-identical from run to run.  No host read, no allocation, no
+ * state: capturable into a HIP graph. */
+size_t mgs_pointwise_wide_workspace_bytes(int64_t B, int Cin, int Cout, int64_t n);
+int mgs_pointwise_wide_forward(int64_t B, int Cin, int Cout, int64_t n, const float* x, const float* w, const float* bias, float* y,
+                               mgs_stream_t stream);
+int mgs_pointwise_wide_backward(int64_t B, int Cin, int Cout, int64_t n, const float* x, const float* g_y, const float* w, float* dx,
+                                float* dw, float* db, void* workspace, size_t workspace_bytes, int split, mgs_stream_t stream);
+
 /* ---- the Perceiver decoder's narrow-output 3x3x3 convolution with its pad folded into the addressing (SURVEY.md 2:
  * agents/manigaussian_bc/perceiver_lang_io.py:322, trans_decoder = nn.Conv3d(128, 1, 3, padding=1, padding_mode='replicate') with
  * bias) -- additive exports, ABI v17 ----

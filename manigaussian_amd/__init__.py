@@ -18,7 +18,7 @@ from .volume import Conv3DBlock, Conv3DUpsampleBlock, resample_pad  # noqa: F401
 from .feedforward import GEGLU, FeedForward, PreNorm, bias_geglu, layer_norm  # noqa: F401
 from .encoder import ConvBnReLU3D, InPlaceABN, MultiLayer3DEncoderShallow, batch_norm_act  # noqa: F401
 from .conv3d import conv3d, conv_transpose3d  # noqa: F401
-from .pointwise import pointwise_conv3d  # noqa: F401
+from .pointwise import pointwise_conv3d, wide_pointwise_conv3d  # noqa: F401
 from .narrow import narrow_conv3d  # noqa: F401
 from .dense import dense_conv3d  # noqa: F401
 from .patch import patch_conv3d  # noqa: F401

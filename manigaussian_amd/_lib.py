@@ -279,6 +279,10 @@ _EXPORTS = {
     "mgs_pointwise_forward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [c_fp] * 5),
     "mgs_pointwise_backward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [c_fp] * 7 +
                                [c_sz, ctypes.c_int, c_fp]),
+    "mgs_pointwise_wide_workspace_bytes": (c_sz, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
+    "mgs_pointwise_wide_forward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [c_fp] * 5),
+    "mgs_pointwise_wide_backward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [c_fp] * 7 +
+                                    [c_sz, ctypes.c_int, c_fp]),
     "mgs_narrow_conv3d_workspace_bytes": (c_sz, [ctypes.c_int64, ctypes.c_int, ctypes.c_int] + [ctypes.c_int64] * 3),
     "mgs_narrow_conv3d_forward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int] + [ctypes.c_int64] * 3 + [ctypes.c_int] +
                                   [c_fp] * 5),

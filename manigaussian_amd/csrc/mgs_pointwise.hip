@@ -33,6 +33,17 @@
 // in double: dw and db are the same bits for every split.  Above 16 input channels the launch is repeated per group of 16 input
 // channels, re-reading g (the accumulators of more do not fit a lane).
 //
+// The wide op (mgs_pointwise_wide_*: Cin 1..16, Cout 65..256; conv_out at final_dim = 128 is 8 -> 128).  Forward and the input
+// gradient alone are the kernels above as they are: pw_fwd_narrow_kernel walks any number of output channels, pw_fwd_wide_kernel<TRANS>
+// any number of looped ones.  The fused backward is pw_bwd_kernel<.., BLOCKS>: 8 waves of 8 output channels are a BLOCK of 64, and a
+// workgroup walks its run of tiles once per block, in ascending order, with the same registers as the narrow op's single pass.  g is
+// read once, x once per block; dx is written once per block, and from the second block on a thread first reads back what IT stored
+// for the element in the block before and adds the waves' shares to that -- one chain over the groups of 8 output channels in
+// ascending order, the TRANS forward's association, so dx is the same bits whether or not dw and db are asked for.  (DERIVED: 168
+// rows of n floats at 8 -> 128 against 144 if both blocks' accumulators were live at once, which 256 VGPRs do not hold beside the
+// double-buffered g.)  Up to 8 input channels the read-back is the first load of a tile, in flight while the tile is worked on;
+// above 8 the registers for that are not there and it is issued behind the tile's barrier.
+//
 // Element offsets are 64-bit; n < 2^31.
 #include "mgs_common.h"
 
@@ -47,6 +58,9 @@ constexpr int PW_BWD_WAVES = 8;             // waves per workgroup of the backwa
 constexpr int PW_BWD_THREADS = 64 * PW_BWD_WAVES;
 constexpr int PW_BWD_COG = 8;               // output channels per wave of the backward
 constexpr int PW_BWD_CIG = 16;              // most input channels per launch of the backward
+constexpr int PW_BWD_BLOCK = PW_BWD_WAVES * PW_BWD_COG;   // output channels per pass of a workgroup over its run
+constexpr int PW_WIDE_MAX_CIN = PW_BWD_CIG; // the wide op (mgs_pointwise_wide_*): what the fused backward holds per lane ...
+constexpr int PW_WIDE_MIN_COUT = PW_MAX_C + 1, PW_WIDE_MAX_COUT = 256;   // ... and the output channels the narrow op does not take
 
 // NV values of the row `row` (n long) for the tile that starts at voxel v0: VEC: voxels v0 + pos NV .. + NV - 1 in one access (n and
 // v0 are multiples of NV, the row starts on a 16-byte boundary); else voxels v0 + pos + k LANES, one word each.  Voxels past n are 0,
@@ -278,24 +292,35 @@ __device__ __forceinline__ void pw_dx_share(const float (&cur)[COG][VPL], const 
   }
 }
 
-template <int CI, int VPL, bool VEC>
+// BLOCKS (the wide op: more than PW_BWD_BLOCK = 64 output channels, one launch, ci0 = 0): a run is walked once per block of 64 output
+// channels, in ascending order.  In block c wave k owns channels 64 c + 8 k .. + 7 and writes those rows of the run's record.  In a
+// block after the first a dx element's sum starts from what the SAME thread stored for it in the block before, and the waves'
+// shares are added to that in ascending wave order: dx is one chain over the groups of 8 output channels in ascending order, the
+// association of the TRANS forward.  Without BLOCKS there is the one block, taken before the runs as ever.
+template <int CI, int VPL, bool VEC, bool BLOCKS = false>
 __global__ __launch_bounds__(PW_BWD_THREADS) void pw_bwd_kernel(PwBwd a) {
   constexpr int COG = PW_BWD_COG, TV = 64 * VPL;
+  constexpr int UNITS = CI * 64 / PW_BWD_THREADS;                 // (input channel, lane) units of dx per thread
   __shared__ __attribute__((aligned(16))) float part[PW_BWD_WAVES * CI * TV];   // [wave][input channel][voxel of the tile]
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int co0 = wave * COG;
-  const int nco = min(max(a.Cout - co0, 0), COG);                 // this wave's output channels (0: it only helps to add up dx)
-  const int nwave = (a.Cout + COG - 1) / COG;                     // waves that own output channels
   const bool want_dx = a.dx != nullptr;
   const int64_t n = a.n;
+  const int nblk = BLOCKS ? (a.Cout + PW_BWD_BLOCK - 1) / PW_BWD_BLOCK : 1;
+  int co0, nco, nwave;
   PwWeights<COG, CI> wt;
-  if (want_dx) {
-    wt.load(a.w, co0, nco, a.ci0, a.nci, a.Cin, lane);
-  } else {   // (w may be NULL then)
+  auto take_block = [&](int cb) {
+    co0 = cb * PW_BWD_BLOCK + wave * COG;
+    nco = min(max(a.Cout - co0, 0), COG);                         // this wave's output channels (0: it only helps to add up dx)
+    nwave = (min(a.Cout - cb * PW_BWD_BLOCK, PW_BWD_BLOCK) + COG - 1) / COG;   // waves that own output channels
+    if (want_dx) {
+      wt.load(a.w, co0, nco, a.ci0, a.nci, a.Cin, lane);
+    } else {   // (w may be NULL then)
 #pragma unroll
-    for (int h = 0; h < PwWeights<COG, CI>::NW; ++h) wt.r[h] = 0.f;
-  }
+      for (int h = 0; h < PwWeights<COG, CI>::NW; ++h) wt.r[h] = 0.f;
+    }
+  };
+  if (!BLOCKS) take_block(0);
 
   // the rows of tile t: g of this wave's output channels, x of the launch's input channels (rows that do not exist: zeros)
   auto fetch_g = [&](float (&gv)[COG][VPL], uint32_t t) {   // (the zeros are put in when the tile becomes the current one)
@@ -311,7 +336,10 @@ __global__ __launch_bounds__(PW_BWD_THREADS) void pw_bwd_kernel(PwBwd a) {
       pw_load<VPL, 64, VEC>(xv[ci], a.x + ((int64_t)b * a.Cin + a.ci0 + min(ci, a.nci - 1)) * n, (int64_t)vt * TV, lane, n, ci < a.nci);
   };
 
-  for (uint32_t rec = blockIdx.x; rec < a.nrec; rec += gridDim.x) {
+  for (uint32_t rec = blockIdx.x; rec < a.nrec; rec += gridDim.x)
+  for (int cb = 0; cb < nblk; ++cb) {   // (one block, taken above, without BLOCKS)
+    if (BLOCKS) take_block(cb);
+    const bool later = BLOCKS && cb > 0 && want_dx;   // dx holds the sum over the blocks before this one
     float acc[COG][CI + 1];
 #pragma unroll
     for (int j = 0; j < COG; ++j)
@@ -324,6 +352,18 @@ __global__ __launch_bounds__(PW_BWD_THREADS) void pw_bwd_kernel(PwBwd a) {
     for (uint32_t t = t0; t < t1; ++t) {
       const uint32_t b = t / a.tiles_per_row, vt = t - b * a.tiles_per_row;
       const int64_t v0 = (int64_t)vt * TV;
+      // what this thread stored into its units of dx in the block before (behind a uniform branch).  A voxel or channel that is not
+      // there loads one that is and is not stored.  With VPL = 4 it is the first of the tile's loads, in flight while the tile is
+      // worked on; with VPL = 2 the registers for that are not there, and it is asked for behind the barrier, the tile's g and x spent.
+      float prev[UNITS][VPL];
+      auto fetch_prev = [&]() {
+#pragma unroll
+        for (int i = 0; i < UNITS; ++i) {
+          const int u = threadIdx.x + i * PW_BWD_THREADS;
+          pw_fetch<VPL, 64, VEC>(prev[i], a.dx + ((int64_t)b * a.Cin + min(u >> 6, a.nci - 1)) * n, v0, u & 63, n);
+        }
+      };
+      if (later && VPL == 4) fetch_prev();
       if (nco > 0) {   // (uniform across the wave)
         float cur[COG][VPL], xv[CI][VPL];
 #pragma unroll
@@ -359,18 +399,29 @@ __global__ __launch_bounds__(PW_BWD_THREADS) void pw_bwd_kernel(PwBwd a) {
       }
       if (want_dx) {
         __syncthreads();
-        // the waves' shares, added in ascending wave order: one (input channel, lane) unit of VPL voxels per step
-        for (int u = threadIdx.x; u < CI * 64; u += PW_BWD_THREADS) {
+        if (later && VPL != 4) fetch_prev();
+        // the waves' shares, added in ascending wave order (in a later block: to `before`, the blocks before this one): one (input
+        // channel, lane) unit of VPL voxels per step
+        auto add_up = [&](int u, const float (&before)[VPL]) {
           const int ci = u >> 6, l = u & 63;
           if (ci < a.nci) {
             float s[VPL];
 #pragma unroll
-            for (int k = 0; k < VPL; ++k) s[k] = part[ci * TV + (VEC ? l * VPL + k : k * 64 + l)];
+            for (int k = 0; k < VPL; ++k) {
+              s[k] = part[ci * TV + (VEC ? l * VPL + k : k * 64 + l)];
+              if (later) s[k] = before[k] + s[k];
+            }
             for (int wv = 1; wv < nwave; ++wv)
 #pragma unroll
               for (int k = 0; k < VPL; ++k) s[k] += part[(wv * CI + ci) * TV + (VEC ? l * VPL + k : k * 64 + l)];
             pw_store<VPL, 64, VEC>(s, a.dx + ((int64_t)b * a.Cin + a.ci0 + ci) * n, v0, l, n);
           }
+        };
+        if (BLOCKS) {
+#pragma unroll
+          for (int i = 0; i < UNITS; ++i) add_up(threadIdx.x + i * PW_BWD_THREADS, prev[i]);
+        } else {
+          for (int u = threadIdx.x; u < CI * 64; u += PW_BWD_THREADS) add_up(u, prev[0]);
         }
         __syncthreads();
       }
@@ -398,8 +449,12 @@ struct PwShape {
   int64_t tiles_per_row, ntiles, nrec, tpr;   // the backward's tiles, runs and tiles per run
 };
 
-static bool pw_shape(int64_t B, int Cin, int Cout, int64_t n, PwShape* sh, const char** why) {
-  if (Cin < 1 || Cin > PW_MAX_C || Cout < 1 || Cout > PW_MAX_C) { *why = "channel counts must be 1 to 64"; return false; }
+// wide: the limits of mgs_pointwise_wide_* (everything else is the same)
+static bool pw_shape(int64_t B, int Cin, int Cout, int64_t n, PwShape* sh, const char** why, bool wide = false) {
+  if (wide) {
+    if (Cin < 1 || Cin > PW_WIDE_MAX_CIN) { *why = "Cin must be 1 to 16"; return false; }
+    if (Cout < PW_WIDE_MIN_COUT || Cout > PW_WIDE_MAX_COUT) { *why = "Cout must be 65 to 256"; return false; }
+  } else if (Cin < 1 || Cin > PW_MAX_C || Cout < 1 || Cout > PW_MAX_C) { *why = "channel counts must be 1 to 64"; return false; }
   if (B < 1 || n < 1) { *why = "B and n must be at least 1"; return false; }
   if (row_too_long(1, 1, n)) { *why = "a (batch, channel) row must hold fewer than 2^31 elements"; return false; }
   const int64_t lim = 0x7fffffff;
@@ -417,9 +472,9 @@ static bool pw_shape(int64_t B, int Cin, int Cout, int64_t n, PwShape* sh, const
   return true;
 }
 
-static int pw_check(const char* fn, int64_t B, int Cin, int Cout, int64_t n, PwShape* sh) {
+static int pw_check(const char* fn, int64_t B, int Cin, int Cout, int64_t n, PwShape* sh, bool wide = false) {
   const char* why = "";
-  if (!pw_shape(B, Cin, Cout, n, sh, &why)) {
+  if (!pw_shape(B, Cin, Cout, n, sh, &why, wide)) {
     set_error("%s: B = %lld, Cin = %d, Cout = %d, n = %lld: %s", fn, (long long)B, Cin, Cout, (long long)n, why);
     return MGS_ERR_INVALID_ARG;
   }
@@ -457,24 +512,19 @@ static void pw_launch_forward(const PwShape& sh, int Cl, int Co, bool trans, con
 #undef PW_FWD
 }
 
-}  // namespace mgs
-
-using namespace mgs;
-
-extern "C" {
-
-size_t mgs_pointwise_workspace_bytes(int64_t B, int Cin, int Cout, int64_t n) {
+// ---- the entry points' bodies: mgs_pointwise_* and, wide, mgs_pointwise_wide_* (its limits, and the backward walks blocks of 64
+// output channels) -----------------------------------------------------------------------------------------------------------------
+static size_t pw_workspace_bytes(int64_t B, int Cin, int Cout, int64_t n, bool wide) {
   PwShape sh;
   const char* why;
-  if (!pw_shape(B, Cin, Cout, n, &sh, &why)) return 0;
+  if (!pw_shape(B, Cin, Cout, n, &sh, &why, wide)) return 0;
   return align_up((size_t)sh.nrec * (size_t)Cout * (size_t)(Cin + 1) * sizeof(float)) + ALIGN;
 }
 
-int mgs_pointwise_forward(int64_t B, int Cin, int Cout, int64_t n, const float* x, const float* w, const float* bias, float* y,
-                          mgs_stream_t stream) {
-  const char* fn = "pointwise_forward";
+static int pw_forward(const char* fn, bool wide, int64_t B, int Cin, int Cout, int64_t n, const float* x, const float* w,
+                      const float* bias, float* y, mgs_stream_t stream) {
   PwShape sh;
-  if (int rc = pw_check(fn, B, Cin, Cout, n, &sh)) return rc;
+  if (int rc = pw_check(fn, B, Cin, Cout, n, &sh, wide)) return rc;
   if (!x || !w || !y) { set_error("%s: NULL x, w or y", fn); return MGS_ERR_INVALID_ARG; }
   if (misaligned16(x) || misaligned16(w) || misaligned16(y) || misaligned16(bias)) {
     set_error("%s: x, w, bias and y must be 16-byte aligned", fn);
@@ -484,11 +534,11 @@ int mgs_pointwise_forward(int64_t B, int Cin, int Cout, int64_t n, const float* 
   return launch_done(fn);
 }
 
-int mgs_pointwise_backward(int64_t B, int Cin, int Cout, int64_t n, const float* x, const float* g_y, const float* w, float* dx,
-                           float* dw, float* db, void* workspace, size_t workspace_bytes, int split, mgs_stream_t stream) {
-  const char* fn = "pointwise_backward";
+static int pw_backward(const char* fn, bool wide, int64_t B, int Cin, int Cout, int64_t n, const float* x, const float* g_y,
+                       const float* w, float* dx, float* dw, float* db, void* workspace, size_t workspace_bytes, int split,
+                       mgs_stream_t stream) {
   PwShape sh;
-  if (int rc = pw_check(fn, B, Cin, Cout, n, &sh)) return rc;
+  if (int rc = pw_check(fn, B, Cin, Cout, n, &sh, wide)) return rc;
   if (int rc = split_check(fn, split)) return rc;
   if (!dx && !dw && !db) { set_error("%s: NULL dx, dw and db: no gradient is asked for", fn); return MGS_ERR_INVALID_ARG; }
   const bool sums = dw || db;
@@ -502,7 +552,7 @@ int mgs_pointwise_backward(int64_t B, int Cin, int Cout, int64_t n, const float*
     pw_launch_forward(sh, Cout, Cin, true, g_y, w, nullptr, dx, s);
     return launch_done(fn);
   }
-  if (int rc = records_workspace(fn, workspace, workspace_bytes, mgs_pointwise_workspace_bytes(B, Cin, Cout, n))) return rc;
+  if (int rc = records_workspace(fn, workspace, workspace_bytes, pw_workspace_bytes(B, Cin, Cout, n, wide))) return rc;
   const int64_t wgs = split_clamp(split, MAX_REC, sh.nrec);
   PwBwd a;
   a.Cin = Cin; a.Cout = Cout; a.n = n;
@@ -511,8 +561,19 @@ int mgs_pointwise_backward(int64_t B, int Cin, int Cout, int64_t n, const float*
   a.x = x; a.g = g_y; a.w = w; a.dx = dx;
   a.records = reinterpret_cast<float*>(workspace);
   const dim3 grid((unsigned)wgs), block(PW_BWD_THREADS);
+  if (wide) {   // up to 16 input channels: one launch, g read once; the blocks of 64 output channels inside it
+    a.ci0 = 0;
+    a.nci = Cin;
+    if (sh.vpl == 4) {
+      if (sh.vec) hipLaunchKernelGGL((pw_bwd_kernel<8, 4, true, true>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((pw_bwd_kernel<8, 4, false, true>), grid, block, 0, s, a);
+    } else {
+      if (sh.vec) hipLaunchKernelGGL((pw_bwd_kernel<16, 2, true, true>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((pw_bwd_kernel<16, 2, false, true>), grid, block, 0, s, a);
+    }
+  }
   // more than 16 input channels: one launch per group of 16, each reading g again
-  for (int ci0 = 0; ci0 < Cin; ci0 += PW_BWD_CIG) {
+  for (int ci0 = 0; !wide && ci0 < Cin; ci0 += PW_BWD_CIG) {
     a.ci0 = ci0;
     a.nci = Cin - ci0 < PW_BWD_CIG ? Cin - ci0 : PW_BWD_CIG;
     if (sh.vpl == 4) {
@@ -525,6 +586,39 @@ int mgs_pointwise_backward(int64_t B, int Cin, int Cout, int64_t n, const float*
   }
   launch_records_merge(sh.nrec, Cout, Cin + 1, Cin, a.records, dw, db, s);
   return launch_done(fn);
+}
+
+}  // namespace mgs
+
+using namespace mgs;
+
+extern "C" {
+
+size_t mgs_pointwise_workspace_bytes(int64_t B, int Cin, int Cout, int64_t n) { return pw_workspace_bytes(B, Cin, Cout, n, false); }
+
+int mgs_pointwise_forward(int64_t B, int Cin, int Cout, int64_t n, const float* x, const float* w, const float* bias, float* y,
+                          mgs_stream_t stream) {
+  return pw_forward("pointwise_forward", false, B, Cin, Cout, n, x, w, bias, y, stream);
+}
+
+int mgs_pointwise_backward(int64_t B, int Cin, int Cout, int64_t n, const float* x, const float* g_y, const float* w, float* dx,
+                           float* dw, float* db, void* workspace, size_t workspace_bytes, int split, mgs_stream_t stream) {
+  return pw_backward("pointwise_backward", false, B, Cin, Cout, n, x, g_y, w, dx, dw, db, workspace, workspace_bytes, split, stream);
+}
+
+// Cin 1..16, Cout 65..256: the same forward kernels (x in registers, any number of output channels; the input gradient alone is the
+// TRANS forward), and the fused backward over blocks of 64 output channels
+size_t mgs_pointwise_wide_workspace_bytes(int64_t B, int Cin, int Cout, int64_t n) { return pw_workspace_bytes(B, Cin, Cout, n, true); }
+
+int mgs_pointwise_wide_forward(int64_t B, int Cin, int Cout, int64_t n, const float* x, const float* w, const float* bias, float* y,
+                               mgs_stream_t stream) {
+  return pw_forward("pointwise_wide_forward", true, B, Cin, Cout, n, x, w, bias, y, stream);
+}
+
+int mgs_pointwise_wide_backward(int64_t B, int Cin, int Cout, int64_t n, const float* x, const float* g_y, const float* w, float* dx,
+                                float* dw, float* db, void* workspace, size_t workspace_bytes, int split, mgs_stream_t stream) {
+  return pw_backward("pointwise_wide_backward", true, B, Cin, Cout, n, x, g_y, w, dx, dw, db, workspace, workspace_bytes, split,
+                     stream);
 }
 
 }  // extern "C"

@@ -14,7 +14,8 @@ initialisation (InPlaceABN keeps a real nn.BatchNorm3d as `bn`): the stem's 62 s
 way round.  The 3x3x3 convolutions are nn.Conv3d / nn.ConvTranspose3d modules whose weights go through conv3d / conv_transpose3d
 (conv3d.py, csrc/mgs_conv3d.hip) where conv_site() says so (CONV overrides it; a CPU tensor, another dtype, a bias or any other
 kernel size, padding, dilation or groups stays torch's).  The 1x1x1 conv_out with bias goes through pointwise_conv3d (pointwise.py,
-csrc/mgs_pointwise.hip) where pointwise_site() says so (POINTWISE overrides it).  The stem hands conv4 / conv2 / conv0 to its three
+csrc/mgs_pointwise.hip) where pointwise_site() says so (POINTWISE overrides it), and with 65..256 output channels (out_channels = 128,
+the reference's final_dim) through wide_pointwise_conv3d where wide_pointwise_site() says so.  The stem hands conv4 / conv2 / conv0 to its three
 transposed-convolution sites as the skip tensor.  A site runs the reference's torch composition on a CPU tensor, for a dtype other than float32, for momentum=None, in
 eval mode with gradients enabled -- and wherever fused_site() says the fused op was not measured faster (FORCE overrides it).
 """
@@ -23,7 +24,7 @@ from torch import nn
 
 from . import _conv, _lib, _ops
 from .conv3d import conv3d, conv_transpose3d
-from .pointwise import pointwise_conv3d
+from .pointwise import WIDE_MAX_CIN, WIDE_MAX_COUT, WIDE_MIN_COUT, pointwise_conv3d, wide_pointwise_conv3d
 
 MAX_C = 65536
 MAX_CONV_C = 64
@@ -131,6 +132,39 @@ def _pointwise_routed(conv, x):
     if x[0, 0].numel() >= 2 ** 31:
         return False
     return True if POINTWISE else pointwise_site(conv.in_channels, conv.out_channels, x.numel() // x.size(1))
+
+
+# The same conv_out with 65..256 output channels (out_channels = 128) through wide_pointwise_conv3d.  It follows the switches above:
+# POINTWISE = None: wide_pointwise_site(); True / False: every eligible site / none.
+WIDE_POINTWISE_CHANNELS = (8, 128)  # the channel counts that were measured (conv_out's at final_dim = 128)
+WIDE_POINTWISE_MIN_VALUES = 100 ** 3  # B D H W of the smallest measured winner, [1, 8 -> 128, 100^3] (None: no shape won all four pairs)
+
+
+def wide_pointwise_site(cin, cout, values_per_channel):
+    """The routing rule of the 1x1x1 convolution with 65..256 output channels (values_per_channel = B D H W), from the measurement
+    (scripts/bench_wide_pointwise.py -> profiles/wide_pointwise_bench.json), by fused_site()'s criterion, as
+    pointwise_site().  Measured on an MI355X at 8 -> 128 channels, B = 1: at 100^3 the op wins the forward 2.2 x and forward +
+    backward 198 x (0.67 against 132.5 ms: torch's weight and bias gradient alone takes 131.9 ms).  At 50^3 it wins forward + backward
+    84 x but its forward ties torch's (44.6 against 43.9 us eager, 50.0 against 49.4 us graph-replayed), and at 25^3 the forward loses
+    2.7 x: neither is routed, and POINTWISE = True is the caller's switch there.  Nothing is routed below the smallest measured
+    winner's size or at channel counts nobody measured."""
+    if WIDE_POINTWISE_MIN_VALUES is None:
+        return False
+    return (cin, cout) == WIDE_POINTWISE_CHANNELS and values_per_channel >= WIDE_POINTWISE_MIN_VALUES
+
+
+def _wide_pointwise_routed(conv, x):
+    """_pointwise_routed's questions for 1..16 input and 65..256 output channels."""
+    w = conv.weight
+    if POINTWISE is False or FORCE is False or not _conv.routable(x, w, conv.bias):
+        return False
+    if conv.kernel_size != (1, 1, 1) or conv.stride != (1, 1, 1) or conv.padding != (0, 0, 0) or conv.dilation != (1, 1, 1):
+        return False
+    if conv.groups != 1 or conv.padding_mode != "zeros" or x.size(1) != conv.in_channels:
+        return False
+    if not (1 <= w.size(1) <= WIDE_MAX_CIN and WIDE_MIN_COUT <= w.size(0) <= WIDE_MAX_COUT) or x[0, 0].numel() >= 2 ** 31:
+        return False
+    return True if POINTWISE else wide_pointwise_site(conv.in_channels, conv.out_channels, x.numel() // x.size(1))
 
 
 class _BatchNormAct(torch.autograd.Function):
@@ -326,4 +360,6 @@ class MultiLayer3DEncoderShallow(nn.Module):
         del conv0
         if _pointwise_routed(self.conv_out, x):
             return pointwise_conv3d(x, self.conv_out.weight, self.conv_out.bias), voxel_list
+        if _wide_pointwise_routed(self.conv_out, x):
+            return wide_pointwise_conv3d(x, self.conv_out.weight, self.conv_out.bias), voxel_list
         return self.conv_out(x), voxel_list
